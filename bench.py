@@ -24,9 +24,12 @@ value = RunPatchMatch pixels processed by all ranks (2 passes x views x W x H)
 / max-over-ranks wall time of the K timed steps, in Mpix/s (per pass; a
 reference view's photometric + geometric result is value / 2).
 
-Rank 0 at N=1 also runs, BEFORE touching the GPU, two rocprofv3 counter
-passes of one step (tools/bench_pmc.py) for the roofline block, and after the
-timed region the CPU oracle on a bounded sample (cpu_baseline).
+A plain run sets up, warms up, times the K steps and prints the result line
+(`--dump-outputs DIR` also saves what the last timed step computed). With
+`--full`, rank 0 at N=1 also runs, BEFORE touching the GPU, the rocprofv3
+counter passes of one step (tools/bench_pmc.py) and, after the timed region,
+one view alone on one stream for the roofline block and the CPU oracle on a
+bounded sample (cpu_baseline).
 """
 from __future__ import annotations
 
@@ -66,14 +69,20 @@ def parse(argv=None):
     ap.add_argument("--width", type=int, default=1600)
     ap.add_argument("--height", type=int, default=1200)
     ap.add_argument("--iters", type=int, default=8)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the counter passes and the isolated "
+                         "launch of the roofline block, and the CPU baseline (see --pmc, --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, save the last step's planes, costs and photometric depth maps "
+                         "of the owned views as DIR/<name>.npy (a fixed pixel sample when they exceed the budget)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--cpu-sample", default="800x600", help="ref-view crop timed on the CPU oracle")
     ap.add_argument("--streams", type=int, default=2,
                     help="engines (HIP streams) per GPU running different views concurrently")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="collective backend (nccl = RCCL over xGMI; gloo only to test on one GPU)")
     ap.add_argument("--pmc", default="auto", choices=["auto", "off"],
-                    help="in-run rocprofv3 counter passes for the roofline (rank 0, N=1)")
+                    help="with --full: in-run rocprofv3 counter passes for the roofline (rank 0, N=1)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     # tests only (tests/test_gpu_bench_exchange.py): one process holding the
     # views of every rank of a world of this size, no collective; and the
@@ -93,6 +102,42 @@ def view_sources(k: int, rank: int, world: int, views: int, pairs, nsrc: int) ->
     reference's source lists span views, src/ACMMP.cpp:619-634; at world 1
     every source is the rank's own copy)."""
     return [((rank + 1 + j) % world) * views + pairs[k][j] for j in range(nsrc)]
+
+
+DUMP_BUDGET_BYTES = 48 << 20  # of --dump-outputs, all files together
+DUMP_SEED = 20240  # of the pixel sample taken when the outputs exceed the budget
+DUMP_NAN, DUMP_INF = -1.0e6, 3.0e38  # finite float32 stand-ins for NaN and +-inf in the saved arrays
+
+
+def dump_outputs(folder: str, rv, mine) -> None:
+    """What the timed path left after its last step, as float32 .npy files
+    with the owned views stacked in the order of view_ids.npy: the geometric
+    pass's planes (views, pixels, 4: normal and depth) and costs (views,
+    pixels) and the photometric depth maps the exchange carried (views,
+    pixels). `pixels` are the row-major pixel indices y * W + x listed in
+    pixels.npy (float64, ascending): every pixel when that fits the budget,
+    else a seeded sample that depends only on the image size, the view count
+    and the constants above, the same for every view and every run.
+    A pixel the algorithm leaves without a cost holds NaN in the resident
+    state (as the reference computes it); every saved value is finite, so
+    NaN is written as DUMP_NAN, a value no cost, normal or depth takes, and
+    an infinity as +-DUMP_INF."""
+    n, H, W = rv.costs.shape
+    per_pixel = n * (4 + 1 + 1) * 4 + 8  # three float32 arrays and the float64 index
+    count = min(H * W, DUMP_BUDGET_BYTES // per_pixel)
+    if count < H * W:
+        pix = np.sort(np.random.default_rng(DUMP_SEED).choice(H * W, size=count, replace=False))
+    else:
+        pix = np.arange(H * W)
+    os.makedirs(folder, exist_ok=True)
+    np.save(os.path.join(folder, "view_ids.npy"), np.asarray(mine, dtype=np.float64))
+    np.save(os.path.join(folder, "pixels.npy"), pix.astype(np.float64))
+    import torch
+    idx = torch.from_numpy(pix).to(rv.costs.device)
+    for name, t in (("geom_planes", rv.planes.reshape(n, H * W, 4)), ("geom_costs", rv.costs.reshape(n, H * W)),
+                    ("photo_depth", rv.my_depth.reshape(n, H * W))):
+        a = torch.nan_to_num(t.index_select(1, idx), nan=DUMP_NAN, posinf=DUMP_INF, neginf=-DUMP_INF).cpu().numpy()
+        np.save(os.path.join(folder, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def host_cpu():
@@ -116,13 +161,13 @@ def main():
     world_env = int(os.environ.get("WORLD_SIZE", "1"))
     rank_env = int(os.environ.get("RANK", "0"))
     pmc = None
-    if args.pmc == "auto" and not args.pmc_child and "WORLD_SIZE" not in os.environ:
+    if args.full and args.pmc == "auto" and not args.pmc_child and "WORLD_SIZE" not in os.environ:
         # counter passes first: child processes, before this process touches the GPU
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         import bench_pmc
         child = ["--views", str(args.views), "--nsrc", str(args.nsrc), "--width", str(args.width),
                  "--height", str(args.height), "--iters", str(args.iters), "--steps", "1", "--warmup", "0"]
-        pmc = bench_pmc.collect(os.path.abspath(__file__), child, os.path.join(ROOT, "gpurun_out", "bench_pmc"))
+        pmc = bench_pmc.collect(os.path.abspath(__file__), child, os.path.join(ROOT, "bench_out", "pmc"))
 
     import torch
     import torch.distributed as dist
@@ -238,23 +283,27 @@ def main():
             np.save(os.path.join(args.dump, f"geom_planes_{v:03d}.npy"), rv.planes[k].cpu().numpy())
             np.save(os.path.join(args.dump, f"geom_costs_{v:03d}.npy"), rv.costs[k].cpu().numpy())
             np.save(os.path.join(args.dump, f"photo_depth_{v:03d}.npy"), rv.my_depth[k].cpu().numpy())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rv, mine)
     if args.pmc_child or emulate:
         pool.close()
         return
 
-    # one photometric + one geometric view alone on one stream: the
-    # un-overlapped duration of a k_sweep launch (HIP events on the engine's
-    # stream), the denominator of the roofline fractions
-    iso_pool = EnginePool(dev_index, 1, timing=True)
-    eng = iso_pool.engines[0]
-    k0, v0 = work[0]
-    ids0 = [v0] + srcs[v0]
-    photometric_view(iso_pool, eng, photo_params, [cams[i] for i in ids0], [images[i].data_ptr() for i in ids0],
-                     rv.planes[k0].data_ptr(), rv.costs[k0].data_ptr(), rv.my_depth[k0].data_ptr())
-    geometric_view(iso_pool, eng, geom_params, [cams[i] for i in ids0], [images[i].data_ptr() for i in ids0],
-                   [all_depth[i].data_ptr() for i in ids0], rv.planes[k0].data_ptr(), rv.costs[k0].data_ptr())
-    iso_ms = iso_pool.sweep_ms / max(iso_pool.sweep_launches, 1)
-    iso_pool.close()
+    iso_ms = None
+    if args.full:
+        # one photometric + one geometric view alone on one stream: the
+        # un-overlapped duration of a k_sweep launch (HIP events on the engine's
+        # stream), the denominator of the roofline fractions
+        iso_pool = EnginePool(dev_index, 1, timing=True)
+        eng = iso_pool.engines[0]
+        k0, v0 = work[0]
+        ids0 = [v0] + srcs[v0]
+        photometric_view(iso_pool, eng, photo_params, [cams[i] for i in ids0], [images[i].data_ptr() for i in ids0],
+                         rv.planes[k0].data_ptr(), rv.costs[k0].data_ptr(), rv.my_depth[k0].data_ptr())
+        geometric_view(iso_pool, eng, geom_params, [cams[i] for i in ids0], [images[i].data_ptr() for i in ids0],
+                       [all_depth[i].data_ptr() for i in ids0], rv.planes[k0].data_ptr(), rv.costs[k0].data_ptr())
+        iso_ms = iso_pool.sweep_ms / max(iso_pool.sweep_launches, 1)
+        iso_pool.close()
 
     pix_total = 2 * args.views * world * W * H * args.steps
     value = pix_total / elapsed / 1e6
@@ -298,11 +347,12 @@ def main():
             "ranks": rank_fields(rows, args.steps,
                                  ("RCCL" if backend == "nccl" else "gloo") if distributed else None),
         },
-        "roofline": roofline(pmc, iso_ms, logical, timed_ms, timed_launches, streams, num_images=n_img,
-                             pixels_per_launch=P / 2),
     }
+    if args.full:
+        result["roofline"] = roofline(pmc, iso_ms, logical, timed_ms, timed_launches, streams, num_images=n_img,
+                                      pixels_per_launch=P / 2)
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(args, setup, images, cams, srcs, mine, all_depth, value)
     if rank == 0:
         print(json.dumps(result), flush=True)

@@ -40,7 +40,7 @@ case "$mode" in
     for round in 1 2; do
       for spec in "$@"; do
         split_spec "$spec"
-        env ACMMP_LIB=$lib $envv timeout -k 10 240 python3 bench.py --steps 2 --warmup 1 --pmc off --no-cpu-baseline \
+        env ACMMP_LIB=$lib $envv timeout -k 10 240 python3 bench.py --full --steps 2 --warmup 1 --pmc off --no-cpu-baseline \
           > "gpurun_out/ab_bench_${name}_$round.log" 2>&1
         rc=$?; echo "bench $name round $round rc=$rc"; [ $rc -eq 0 ] || exit $rc
         grep -o '"value": [0-9.]*\|"launch_ms": [0-9.]*' "gpurun_out/ab_bench_${name}_$round.log" | tr '\n' ' '; echo

@@ -20,7 +20,7 @@ step() {  # step <timeout> <log> <ok-codes> <cmd...>
 sel=${*:-tests}
 step 1500 tests.log "0 1" python -u -m pytest $sel -m gpu -v --timeout 120 --timeout-method thread
 step 120 smoke.log "0" python -c "import __graft_entry__ as g; g.smoke()"
-step 600 bench.log "0" python3 bench.py
+step 600 bench.log "0" python3 bench.py --full
 grep '^{' gpurun_out/bench.log | tail -n 1 > gpurun_out/bench.json
 step 400 prof.log "0" rocprofv3 --kernel-trace --stats -f csv -d gpurun_out/prof -o run -- \
   python3 bench.py --steps 2 --warmup 1 --pmc off --no-cpu-baseline
