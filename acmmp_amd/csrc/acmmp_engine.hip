@@ -13,6 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <unordered_map>
@@ -38,21 +39,26 @@ struct DevPool {
         cap = (size_t)std::max(0LL, mb) << 20;  // a negative setting means off, not a huge cap
     }
     // hipFree of every cached block of device dev (all devices: dev < 0);
-    // caller holds mu. Returns the bytes given back.
+    // takes mu itself, to collect the blocks, and frees them unlocked: hipFree
+    // waits for the device, and every other engine thread's dev_alloc /
+    // dev_free would wait on mu behind it. Returns the bytes given back.
     size_t release(int dev) {
+        std::vector<void *> blocks;
         size_t n = 0;
-        for (auto it = free_.begin(); it != free_.end();) {
-            if (dev >= 0 && it->first.first != dev) {
-                ++it;
-                continue;
+        {
+            std::lock_guard<std::mutex> g(mu);
+            for (auto it = free_.begin(); it != free_.end();) {
+                if (dev >= 0 && it->first.first != dev) {
+                    ++it;
+                    continue;
+                }
+                n += it->first.second * it->second.size();
+                blocks.insert(blocks.end(), it->second.begin(), it->second.end());
+                it = free_.erase(it);
             }
-            for (void *p : it->second) {
-                (void)hipFree(p);
-                n += it->first.second;
-            }
-            it = free_.erase(it);
+            cached -= n;
         }
-        cached -= n;
+        for (void *p : blocks) (void)hipFree(p);
         return n;
     }
     size_t bytes(int dev) const {
@@ -134,6 +140,21 @@ void stream_give(int dev, hipStream_t s) {
     (void)hipStreamDestroy(s);
 }
 
+// A stream taken for one call: given back once the call has synchronised it
+// (give), destroyed on any other way out (a failed stream may still hold work).
+struct TakenStream {
+    int dev = 0;
+    hipStream_t s = nullptr;
+    hipError_t take(int device) { return stream_take(dev = device, &s); }
+    void give() {
+        stream_give(dev, s);
+        s = nullptr;
+    }
+    ~TakenStream() {
+        if (s) (void)hipStreamDestroy(s);
+    }
+};
+
 hipError_t event_take(int dev, bool timed, hipEvent_t *e) {
     if (devpool().cap) {
         std::lock_guard<std::mutex> g(handles().mu);
@@ -181,12 +202,7 @@ hipError_t acmmp::dev_alloc(void **p, size_t bytes) {
         // the cache may hold what the device lacks: give this device's
         // cached blocks back and try once more
         (void)hipGetLastError();
-        size_t freed = 0;
-        {
-            std::lock_guard<std::mutex> g(pool.mu);
-            freed = pool.release(dev);
-        }
-        if (freed) {
+        if (pool.release(dev)) {
             e = hipMalloc(p, bytes);
             if (e != hipSuccess) (void)hipGetLastError();
         }
@@ -220,20 +236,14 @@ void acmmp::dev_free(void *p, bool synced) {
 namespace {
 
 void free_depths(acmmp_ctx *ctx) {
-    for (auto &p : ctx->own_dep) dfree(p);
-    ctx->own_dep.clear();
+    for (auto &v : ctx->dep) dfree(v.own);
     ctx->dep.clear();
-    ctx->dep_pitch.clear();
-    ctx->dep_w.clear();
-    ctx->dep_h.clear();
     ctx->have_depths = false;
 }
 
 void free_images(acmmp_ctx *ctx) {
-    for (auto &p : ctx->own_img) dfree(p);
-    ctx->own_img.clear();
+    for (auto &v : ctx->img) dfree(v.own);
     ctx->img.clear();
-    ctx->img_pitch.clear();
     free_depths(ctx);
 }
 
@@ -245,11 +255,7 @@ void free_state(acmmp_ctx *ctx) {
         }
         dfree(ctx->d_csv[c]);
     }
-    dfree(ctx->d_rm_plane);
-    dfree(ctx->d_rm_cost);
-    dfree(ctx->d_rm_depth);
-    ctx->depth_ok = false;
-    dfree(ctx->d_rm_sv);
+    ctx->res.release();
     dfree(ctx->d_pre_cost);
     dfree(ctx->d_prior);
     dfree(ctx->d_mask);
@@ -294,24 +300,20 @@ int kv_upload(acmmp_ctx *ctx) {
     kv.prm = ctx->prm;
     for (int i = 0; i < ctx->n; ++i) {
         kv.cam[i] = ctx->cams[i];
-        kv.img[i] = ctx->img[i];
-        kv.ipitch[i] = ctx->img_pitch[i];
-        kv.pad[i] = ctx->pad_use[i];
-        kv.ppitch[i] = ctx->pad_pitch[i];
+        kv.img[i] = ctx->img[i].p;
+        kv.ipitch[i] = ctx->img[i].pitch;
+        kv.pad[i] = ctx->pad[i].use;
+        kv.ppitch[i] = ctx->pad[i].pitch;
         if (i > 0) kv.rel[i] = view_rel(ctx->cams[0], ctx->cams[i]);
         {
             const acmmp_camera &c = ctx->cams[i];
             for (int k = 0; k < 3; ++k) kv.cw[i][k] = -(c.R[k] * c.t[0] + c.R[3 + k] * c.t[1] + c.R[6 + k] * c.t[2]);
         }
-        if (ctx->have_depths) {
-            kv.dep[i] = ctx->dep[i];
-            kv.dpitch[i] = ctx->dep_pitch[i];
-            kv.dw[i] = ctx->dep_w[i];
-            kv.dh[i] = ctx->dep_h[i];
-        } else {
-            kv.dep[i] = nullptr;
-            kv.dpitch[i] = kv.dw[i] = kv.dh[i] = 0;
-        }
+        const ViewPlane d = ctx->have_depths ? ctx->dep[i] : ViewPlane{};
+        kv.dep[i] = d.p;
+        kv.dpitch[i] = d.pitch;
+        kv.dw[i] = d.w;
+        kv.dh[i] = d.h;
     }
     kv.W = ctx->W;
     kv.H = ctx->H;
@@ -323,7 +325,7 @@ int kv_upload(acmmp_ctx *ctx) {
     // ACMMP_WIDE_INDEX=1 forces it (parity tests of that path at small sizes).
     kv.wide = 0;
     for (int i = 1; i < ctx->n; ++i)
-        if ((size_t)ctx->pad_pitch[i] * (ctx->cams[i].height + 2) >= (1u << 24)) kv.wide = 1;
+        if ((size_t)ctx->pad[i].pitch * (ctx->cams[i].height + 2) >= (1u << 24)) kv.wide = 1;
     if (const char *e = std::getenv("ACMMP_WIDE_INDEX"))
         if (e[0] == '1') kv.wide = 1;
     kv.texel = ctx->pad_texel;
@@ -361,7 +363,9 @@ int kv_upload(acmmp_ctx *ctx) {
     return ACMMP_OK;
 }
 
-// y0, y1: the image rows a launch covers (all rows by default)
+// y0, y1: the image rows a launch covers (all rows by default). Any launch
+// may write the results, so they are taken writable: the depth plane counts
+// as stale until a full run says otherwise.
 KState state_of(acmmp_ctx *ctx, int y0 = 0, int y1 = -1) {
     KState st{};
     st.y0 = y0;
@@ -373,10 +377,11 @@ KState state_of(acmmp_ctx *ctx, int y0 = 0, int y1 = -1) {
         st.cost_nx[c] = ctx->d_ccost[c][ctx->cur[c] ^ 1];
         st.sv[c] = ctx->d_csv[c];
     }
-    st.rm_plane = ctx->d_rm_plane;
-    st.rm_cost = ctx->d_rm_cost;
-    st.rm_depth = ctx->d_rm_depth;
-    st.rm_sv = ctx->d_rm_sv;
+    const Results::Writable rm = ctx->res.write();
+    st.rm_plane = rm.plane;
+    st.rm_cost = rm.cost;
+    st.rm_depth = rm.depth;
+    st.rm_sv = rm.sv;
     st.pre_cost = ctx->d_pre_cost;
     st.prior = ctx->d_prior;
     st.mask = ctx->d_mask;
@@ -386,13 +391,16 @@ KState state_of(acmmp_ctx *ctx, int y0 = 0, int y1 = -1) {
 }
 
 
-int upload_pitched(acmmp_ctx *ctx, float *&dst, int &pitch, const float *src, int w, int h, bool device_src) {
-    pitch = pitch_of(w);
-    HIP_TRY(ctx, dalloc(dst, (size_t)pitch * (size_t)h));
-    HIP_TRY(ctx, hipMemsetAsync(dst, 0, (size_t)pitch * h * sizeof(float), ctx->stream));
-    HIP_TRY(ctx, hipMemcpy2DAsync(dst, (size_t)pitch * sizeof(float), src, (size_t)w * sizeof(float),
-                                  (size_t)w * sizeof(float), (size_t)h,
-                                  device_src ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
+// One view's w x h plane: the caller's device pointer (borrow; pitch 0: dense),
+// else a pitched upload of the host array src.
+int set_view_plane(acmmp_ctx *ctx, ViewPlane &v, const float *src, int pitch, int w, int h, bool borrow) {
+    v = ViewPlane{borrow ? src : nullptr, nullptr, borrow ? (pitch ? pitch : w) : pitch_of(w), w, h};
+    if (borrow) return ACMMP_OK;
+    HIP_TRY(ctx, dalloc(v.own, (size_t)v.pitch * (size_t)h));
+    v.p = v.own;
+    HIP_TRY(ctx, hipMemsetAsync(v.own, 0, (size_t)v.pitch * h * sizeof(float), ctx->stream));
+    HIP_TRY(ctx, hipMemcpy2DAsync(v.own, (size_t)v.pitch * sizeof(float), src, (size_t)w * sizeof(float),
+                                  (size_t)w * sizeof(float), (size_t)h, hipMemcpyHostToDevice, ctx->stream));
     return ACMMP_OK;
 }
 
@@ -402,25 +410,14 @@ int set_depths_impl(acmmp_ctx *ctx, const float *const *depths, const int32_t *p
     if (!depths) return set_err(ctx, ACMMP_ERR_ARG, "depths is NULL");
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // previous run may still read the old maps
     free_depths(ctx);
-    ctx->own_dep.assign(ctx->n, nullptr);
-    ctx->dep.assign(ctx->n, nullptr);
-    ctx->dep_pitch.assign(ctx->n, 0);
-    ctx->dep_w.assign(ctx->n, 0);
-    ctx->dep_h.assign(ctx->n, 0);
+    ctx->dep.assign(ctx->n, ViewPlane{});
     for (int i = 0; i < ctx->n; ++i) {
         if (!depths[i]) return set_err(ctx, ACMMP_ERR_ARG, "depth map %d is NULL", i);
         const int w = ctx->cams[i].width, h = ctx->cams[i].height;
-        if (borrow) {
-            ctx->dep[i] = depths[i];
-            ctx->dep_pitch[i] = pitches ? pitches[i] : w;
-            if (ctx->dep_pitch[i] < w) return set_err(ctx, ACMMP_ERR_ARG, "depth pitch %d < width %d", ctx->dep_pitch[i], w);
-        } else {
-            rc = upload_pitched(ctx, ctx->own_dep[i], ctx->dep_pitch[i], depths[i], w, h, false);
-            if (rc) return rc;
-            ctx->dep[i] = ctx->own_dep[i];
-        }
-        ctx->dep_w[i] = w;
-        ctx->dep_h[i] = h;
+        if (borrow && pitches && pitches[i] < w)
+            return set_err(ctx, ACMMP_ERR_ARG, "depth pitch %d < width %d", pitches[i], w);
+        rc = set_view_plane(ctx, ctx->dep[i], depths[i], pitches ? pitches[i] : 0, w, h, borrow);
+        if (rc) return rc;
     }
     ctx->have_depths = true;
     if (!borrow) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -463,6 +460,47 @@ int texel_tries(int tries[2]) {
     return ntry;
 }
 
+// Builds the padded footprint records of n views (clamp-to-edge copies,
+// device-side, ordered on s) in the most compact form every one of them fits,
+// each attempt checked by one device flag (one stream sync): u8 quads (4 B
+// per footprint: every view integer-valued in [0, 255]), then f16 difference
+// quads (8 B: every stored value exact in f16), else the fp32 row-paired form
+// (16 B; queued, not waited for). ACMMP_TEXEL=u8|h16|f32 restricts the
+// attempt to that one form before fp32 (ACMMP_TEXEL_F32=1 = f32): the parity
+// tests of every form. ctx (may be NULL) only receives the error text.
+int build_pad_records(acmmp_ctx *ctx, const ViewPlane *img, PadRecords *pad, int n, uint32_t *d_unfit,
+                      hipStream_t s, int &form_out) {
+    int tries[2];
+    const int ntry = texel_tries(tries);
+    for (int k = 0;; ++k) {
+        const int form = k < ntry ? tries[k] : kTexelF32;
+        if (form != kTexelF32) HIP_TRY(ctx, hipMemsetAsync(d_unfit, 0, sizeof(uint32_t), s));
+        for (int i = 0; i < n; ++i) {
+            PadRecords &r = pad[i];
+            size_t bytes;
+            if (pad_geometry(img[i].w, img[i].h, form, r.pitch, bytes))
+                return set_err(ctx, ACMMP_ERR_UNSUPPORTED, "view %d is %dx%d: above the 2^31-record gather limit", i,
+                               img[i].w, img[i].h);
+            if (r.bytes < bytes) {  // every form's bytes, not only the first tried
+                r.bytes = 0;
+                HIP_TRY(ctx, dalloc(r.own, bytes / sizeof(float)));
+                r.bytes = bytes;
+            }
+            r.use = r.own;
+            HIP_TRY(ctx, launch_pad_form(form, img[i].p, img[i].pitch, img[i].w, img[i].h, r.own, r.pitch, d_unfit, s));
+        }
+        uint32_t unfit = 0;
+        if (form != kTexelF32) {
+            HIP_TRY(ctx, hipMemcpyAsync(&unfit, d_unfit, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            HIP_TRY(ctx, hipStreamSynchronize(s));
+        }
+        if (unfit == 0) {
+            form_out = form;
+            return ACMMP_OK;
+        }
+    }
+}
+
 // Shared by acmmp_set_images / acmmp_set_images_device.
 int set_images_impl(acmmp_ctx *ctx, int num_images, const acmmp_camera *cams, const float *const *images,
                     const int32_t *pitches, int keep_depth_range, bool borrow,
@@ -500,75 +538,27 @@ int set_images_impl(acmmp_ctx *ctx, int num_images, const acmmp_camera *cams, co
         ctx->prm.disparity_min = cams[0].K[0] * ctx->prm.baseline / ctx->prm.depth_max;
         ctx->prm.disparity_max = cams[0].K[0] * ctx->prm.baseline / ctx->prm.depth_min;
     }
-    ctx->own_img.assign(num_images, nullptr);
-    ctx->img.assign(num_images, nullptr);
-    ctx->img_pitch.assign(num_images, 0);
+    ctx->img.assign(num_images, ViewPlane{});
     for (int i = 0; i < num_images; ++i) {
-        if (borrow) {
-            ctx->img[i] = images[i];
-            ctx->img_pitch[i] = pitches ? pitches[i] : cams[i].width;
-        } else {
-            int rc = upload_pitched(ctx, ctx->own_img[i], ctx->img_pitch[i], images[i], cams[i].width,
-                                    cams[i].height, false);
-            if (rc) return rc;
-            ctx->img[i] = ctx->own_img[i];
-        }
+        int rc = set_view_plane(ctx, ctx->img[i], images[i], pitches ? pitches[i] : 0, cams[i].width, cams[i].height,
+                                borrow);
+        if (rc) return rc;
     }
-    // clamp-to-edge padded copies of every view (device-side, stream ordered)
-    if (ctx->pad.size() < (size_t)num_images) {
-        ctx->pad.resize(num_images, nullptr);
-        ctx->pad_bytes.resize(num_images, 0);
-        ctx->pad_pitch.resize(num_images, 0);
-        ctx->pad_use.resize(num_images, nullptr);
-    }
+    if (ctx->pad.size() < (size_t)num_images) ctx->pad.resize(num_images);
     if (tex) {  // prebuilt records of one common form: borrowed, nothing to pad
         for (int i = 0; i < num_images; ++i) {
-            ctx->pad_use[i] = tex[i]->pad;
-            ctx->pad_pitch[i] = tex[i]->pad_pitch;
+            ctx->pad[i].use = tex[i]->pad.use;
+            ctx->pad[i].pitch = tex[i]->pad.pitch;
         }
         ctx->pad_texel = tex[0]->form;
-    } else {
-    // The most compact form every view fits, each attempt checked by one
-    // device flag (one stream sync): u8 quads (4 B per footprint: every view
-    // integer-valued in [0, 255]), then f16 difference quads (8 B: every
-    // stored value exact in f16), else the fp32 row-paired form (16 B).
-    // ACMMP_TEXEL=u8|h16|f32 restricts the attempt to that one form before
-    // fp32 (ACMMP_TEXEL_F32=1 = f32): the parity tests of every form.
-    int tries[2];
-    const int ntry = texel_tries(tries);
-    if (!ctx->d_not_u8) HIP_TRY(ctx, dalloc(ctx->d_not_u8, 1));
-    ctx->pad_texel = -1;
-    for (int k = 0; k <= ntry && ctx->pad_texel < 0; ++k) {
-        const int form = k < ntry ? tries[k] : kTexelF32;
-        if (form != kTexelF32) HIP_TRY(ctx, hipMemsetAsync(ctx->d_not_u8, 0, sizeof(uint32_t), ctx->stream));
-        for (int i = 0; i < num_images; ++i) {
-            const int w = cams[i].width, h = cams[i].height;
-            int pp;
-            size_t bytes;
-            if (pad_geometry(w, h, form, pp, bytes))
-                return set_err(ctx, ACMMP_ERR_UNSUPPORTED, "view %d is %dx%d: above the 2^31-record gather limit", i,
-                               w, h);
-            if (ctx->pad_bytes[i] < bytes) {
-                dfree(ctx->pad[i]);
-                HIP_TRY(ctx, dalloc(ctx->pad[i], bytes / sizeof(float)));
-                ctx->pad_bytes[i] = bytes;
-            }
-            ctx->pad_pitch[i] = pp;
-            ctx->pad_use[i] = ctx->pad[i];
-            HIP_TRY(ctx, launch_pad_form(form, ctx->img[i], ctx->img_pitch[i], w, h, ctx->pad[i], pp, ctx->d_not_u8,
-                                         ctx->stream));
-        }
-        if (form == kTexelF32) {
-            ctx->pad_texel = kTexelF32;
-        } else {
-            uint32_t unfit = 1;
-            HIP_TRY(ctx, hipMemcpyAsync(&unfit, ctx->d_not_u8, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            if (unfit == 0) ctx->pad_texel = form;
-        }
+    } else {  // one common form per engine
+        if (!ctx->d_not_u8) HIP_TRY(ctx, dalloc(ctx->d_not_u8, 1));
+        ctx->pad_texel = -1;
+        int rc = build_pad_records(ctx, ctx->img.data(), ctx->pad.data(), num_images, ctx->d_not_u8, ctx->stream,
+                                   ctx->pad_texel);
+        if (rc) return rc;
     }
-    }  // padded copies
-    if (resize || !ctx->d_rm_plane) {
+    if (resize || !ctx->res.planes()) {
         free_state(ctx);
         const size_t P = (size_t)ctx->W * ctx->H;
         const size_t Pc = (size_t)ctx->Wh * ctx->H;
@@ -579,17 +569,10 @@ int set_images_impl(acmmp_ctx *ctx, int num_images, const acmmp_camera *cams, co
             }
             HIP_TRY(ctx, dalloc(ctx->d_csv[c], Pc));
         }
-        HIP_TRY(ctx, dalloc(ctx->d_rm_plane, P));
-        HIP_TRY(ctx, dalloc(ctx->d_rm_cost, P));
-        HIP_TRY(ctx, dalloc(ctx->d_rm_depth, P));
-        HIP_TRY(ctx, dalloc(ctx->d_rm_sv, P));
+        int rc = ctx->res.alloc(ctx, P);
+        if (rc) return rc;
+        // zero-filled, as the results are (pin: uninitialised pre_costs)
         HIP_TRY(ctx, dalloc(ctx->d_pre_cost, P));
-        // zero-filled state (pin: the reference's never-written host fields,
-        // src/ACMMP.cpp:797-804, and uninitialised pre_costs)
-        HIP_TRY(ctx, hipMemsetAsync(ctx->d_rm_plane, 0, P * sizeof(float4), ctx->stream));
-        HIP_TRY(ctx, hipMemsetAsync(ctx->d_rm_cost, 0, P * sizeof(float), ctx->stream));
-        HIP_TRY(ctx, hipMemsetAsync(ctx->d_rm_depth, 0, P * sizeof(float), ctx->stream));
-        HIP_TRY(ctx, hipMemsetAsync(ctx->d_rm_sv, 0, P * sizeof(uint32_t), ctx->stream));
         HIP_TRY(ctx, hipMemsetAsync(ctx->d_pre_cost, 0, P * sizeof(float), ctx->stream));
         for (int c = 0; c < 2; ++c) HIP_TRY(ctx, hipMemsetAsync(ctx->d_csv[c], 0, Pc * sizeof(uint32_t), ctx->stream));
     }
@@ -604,11 +587,6 @@ float elapsed(hipEvent_t a, hipEvent_t b) {
 }
 
 }  // namespace
-
-namespace acmmp {
-int upload_kv(acmmp_ctx *ctx) { return kv_upload(ctx); }
-KState make_state(acmmp_ctx *ctx) { return state_of(ctx); }
-}  // namespace acmmp
 
 extern "C" {
 
@@ -680,7 +658,7 @@ void acmmp_destroy(acmmp_ctx *ctx) {
     g_frees_synced = clean;  // nothing queued can touch the engine's blocks now: they go to the cache
     free_images(ctx);
     free_state(ctx);
-    for (auto &p : ctx->pad) dfree(p);
+    for (auto &r : ctx->pad) dfree(r.own);
     dfree(ctx->d_not_u8);
     for (int k = 0; k < acmmp_ctx::kSlots; ++k) dfree(ctx->d_kv_ring[k]);
     g_frees_synced = false;
@@ -716,11 +694,7 @@ int acmmp_release_device_cache(int device) {
     if (device >= ndev || device < -1) return ACMMP_ERR_ARG;
     int cur = 0;
     (void)hipGetDevice(&cur);
-    {
-        DevPool &pool = devpool();
-        std::lock_guard<std::mutex> g(pool.mu);
-        pool.release(device);
-    }
+    devpool().release(device);
     {
         std::lock_guard<std::mutex> g(handles().mu);
         for (auto it = handles().streams.begin(); it != handles().streams.end(); ++it) {
@@ -803,65 +777,29 @@ int acmmp_texture_create(int device, const float *d_image, int pitch, int width,
     if (!out || !d_image || width < 2 || height < 1 || pitch < width) return ACMMP_ERR_ARG;
     *out = nullptr;
     if (hipSetDevice(device) != hipSuccess) return ACMMP_ERR_HIP;
-    auto *t = new (std::nothrow) acmmp_texture;
+    std::unique_ptr<acmmp_texture, void (*)(acmmp_texture *)> t(new (std::nothrow) acmmp_texture,
+                                                                acmmp_texture_destroy);
     if (!t) return ACMMP_ERR_HIP;
     t->device = device;
-    t->img = d_image;
-    t->img_pitch = pitch;
-    t->W = width;
-    t->H = height;
-    hipStream_t s = nullptr;
-    uint32_t *d_unfit = nullptr;
-    int rc = ACMMP_OK;
-    if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess ||
-        hipMalloc((void **)&d_unfit, sizeof(uint32_t)) != hipSuccess)
-        rc = ACMMP_ERR_HIP;
+    t->img = ViewPlane{d_image, nullptr, pitch, width, height};
+    TakenStream s;
+    Scratch<uint32_t> d_unfit;
+    HIP_TRY(nullptr, s.take(device));
+    HIP_TRY(nullptr, d_unfit.alloc(1));
     // the most compact form the image fits (the choice set_images makes per problem)
-    int tries[2];
-    const int ntry = texel_tries(tries);
-    t->form = -1;
-    for (int k = 0; rc == ACMMP_OK && k <= ntry && t->form < 0; ++k) {
-        const int form = k < ntry ? tries[k] : kTexelF32;
-        size_t bytes;
-        if (pad_geometry(width, height, form, t->pad_pitch, bytes)) {
-            rc = ACMMP_ERR_UNSUPPORTED;
-            break;
-        }
-        if (bytes > t->pad_bytes) {  // every form's bytes, not only the first tried
-            if (t->pad) (void)hipFree(t->pad);
-            t->pad = nullptr;
-            t->pad_bytes = 0;
-            if (hipMalloc((void **)&t->pad, bytes) != hipSuccess) {
-                rc = ACMMP_ERR_HIP;
-                break;
-            }
-            t->pad_bytes = bytes;
-        }
-        uint32_t unfit = 0;
-        if (hipMemsetAsync(d_unfit, 0, sizeof(uint32_t), s) != hipSuccess ||
-            launch_pad_form(form, d_image, pitch, width, height, t->pad, t->pad_pitch, d_unfit, s) != hipSuccess ||
-            hipMemcpyAsync(&unfit, d_unfit, sizeof(uint32_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess) {
-            rc = ACMMP_ERR_HIP;
-            break;
-        }
-        if (form == kTexelF32 || unfit == 0) t->form = form;
-    }
-    if (d_unfit) (void)hipFree(d_unfit);
-    if (s) (void)hipStreamDestroy(s);
-    if (rc != ACMMP_OK) {
-        acmmp_texture_destroy(t);
-        return rc;
-    }
-    *out = t;
+    const int rc = build_pad_records(nullptr, &t->img, &t->pad, 1, d_unfit, s.s, t->form);
+    if (rc) return rc;
+    HIP_TRY(nullptr, hipStreamSynchronize(s.s));  // complete on return: the fp32 form is only queued
+    s.give();
+    *out = t.release();
     return ACMMP_OK;
 }
 
 void acmmp_texture_destroy(acmmp_texture *t) {
     if (!t) return;
-    if (t->pad) {
+    if (t->pad.own) {
         (void)hipSetDevice(t->device);
-        (void)hipFree(t->pad);
+        dev_free(t->pad.own, false);  // hipFree: engines may still read the records on their streams
     }
     delete t;
 }
@@ -883,11 +821,11 @@ int acmmp_set_images_textures(acmmp_ctx *ctx, int num_images, const acmmp_camera
         const acmmp_texture *t = textures[i];
         if (!t) return set_err(ctx, ACMMP_ERR_ARG, "texture %d is NULL", i);
         if (t->device != ctx->device) return set_err(ctx, ACMMP_ERR_ARG, "texture %d is on device %d", i, t->device);
-        if (t->W != cams[i].width || t->H != cams[i].height)
-            return set_err(ctx, ACMMP_ERR_ARG, "texture %d is %dx%d, camera %dx%d", i, t->W, t->H, cams[i].width,
-                           cams[i].height);
-        imgs[i] = t->img;
-        pitches[i] = t->img_pitch;
+        if (t->img.w != cams[i].width || t->img.h != cams[i].height)
+            return set_err(ctx, ACMMP_ERR_ARG, "texture %d is %dx%d, camera %dx%d", i, t->img.w, t->img.h,
+                           cams[i].width, cams[i].height);
+        imgs[i] = t->img.p;
+        pitches[i] = t->img.pitch;
         common = common && t->form == textures[0]->form;
     }
     // views of different forms (one not 8-bit, say): pad per engine in the common form
@@ -903,29 +841,28 @@ int acmmp_set_depth_maps_device(acmmp_ctx *ctx, const float *const *d_depths, co
     return set_depths_impl(ctx, d_depths, pitches, true);
 }
 
-int acmmp_set_plane_hypotheses(acmmp_ctx *ctx, const float *planes4, const float *costs) {
+namespace {
+int set_planes_impl(acmmp_ctx *ctx, const float *planes4, const float *costs, bool device_src) {
     int rc = check_ready(ctx);
     if (rc) return rc;
     if (!planes4 || !costs) return set_err(ctx, ACMMP_ERR_ARG, "planes/costs NULL");
     const size_t P = (size_t)ctx->W * ctx->H;
-    ctx->depth_ok = false;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_rm_plane, planes4, P * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_rm_cost, costs, P * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const hipMemcpyKind kind = device_src ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    const Results::Writable rm = ctx->res.write();
+    HIP_TRY(ctx, hipMemcpyAsync(rm.plane, planes4, P * sizeof(float4), kind, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(rm.cost, costs, P * sizeof(float), kind, ctx->stream));
+    if (!device_src) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // the host arrays are the caller's again
     ctx->have_state = true;
     return ACMMP_OK;
 }
+}  // namespace
+
+int acmmp_set_plane_hypotheses(acmmp_ctx *ctx, const float *planes4, const float *costs) {
+    return set_planes_impl(ctx, planes4, costs, false);
+}
 
 int acmmp_set_plane_hypotheses_device(acmmp_ctx *ctx, const float *d_planes4, const float *d_costs) {
-    int rc = check_ready(ctx);
-    if (rc) return rc;
-    if (!d_planes4 || !d_costs) return set_err(ctx, ACMMP_ERR_ARG, "planes/costs NULL");
-    const size_t P = (size_t)ctx->W * ctx->H;
-    ctx->depth_ok = false;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_rm_plane, d_planes4, P * sizeof(float4), hipMemcpyDeviceToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_rm_cost, d_costs, P * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
-    ctx->have_state = true;
-    return ACMMP_OK;
+    return set_planes_impl(ctx, d_planes4, d_costs, true);
 }
 
 int acmmp_wait_stream(acmmp_ctx *ctx, void *stream) {
@@ -944,14 +881,16 @@ int acmmp_export_results(acmmp_ctx *ctx, float *d_planes4, float *d_costs, float
     if (rc) return rc;
     const size_t P = (size_t)ctx->W * ctx->H;
     if (d_planes4)
-        HIP_TRY(ctx, hipMemcpyAsync(d_planes4, ctx->d_rm_plane, P * sizeof(float4), hipMemcpyDeviceToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(d_planes4, ctx->res.planes(), P * sizeof(float4), hipMemcpyDeviceToDevice, ctx->stream));
     if (d_costs)
-        HIP_TRY(ctx, hipMemcpyAsync(d_costs, ctx->d_rm_cost, P * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
-    if (d_depth && ctx->depth_ok)  // the depth plane the last full run wrote: a plain copy
-        HIP_TRY(ctx, hipMemcpyAsync(d_depth, ctx->d_rm_depth, P * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(d_costs, ctx->res.costs(), P * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+    size_t stride;
+    const float *depth = ctx->res.depth_source(stride);
+    if (d_depth && stride == sizeof(float))  // the depth plane the last full run wrote: a plain copy
+        HIP_TRY(ctx, hipMemcpyAsync(d_depth, depth, P * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
     else if (d_depth)  // the .w channel: strided 2-D copy, 4 B out of every 16 B
-        HIP_TRY(ctx, hipMemcpy2DAsync(d_depth, sizeof(float), (const char *)ctx->d_rm_plane + 3 * sizeof(float),
-                                      sizeof(float4), sizeof(float), P, hipMemcpyDeviceToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpy2DAsync(d_depth, sizeof(float), depth, stride, sizeof(float), P,
+                                      hipMemcpyDeviceToDevice, ctx->stream));
     return ACMMP_OK;
 }
 
@@ -971,15 +910,13 @@ int set_hierarchy_impl(acmmp_ctx *ctx, const float *scaled_planes4, int scaled_w
                                 device_src ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
     // plane_hypotheses_host[center].w = ref_depth; x, y, z never written (pinned 0)
     const size_t P = (size_t)ctx->W * ctx->H;
+    float4 *rm_plane = ctx->res.write().plane;
     if (device_src) {
-        ctx->depth_ok = false;
-        HIP_TRY(ctx, launch_depth_planes(upsampled_depth, P, ctx->d_rm_plane, ctx->stream));
+        HIP_TRY(ctx, launch_depth_planes(upsampled_depth, P, rm_plane, ctx->stream));
     } else {
         std::vector<float> tmp(P * 4, 0.0f);
         for (size_t i = 0; i < P; ++i) tmp[i * 4 + 3] = upsampled_depth[i];
-        ctx->depth_ok = false;
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_rm_plane, tmp.data(), P * sizeof(float4), hipMemcpyHostToDevice,
-                                    ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(rm_plane, tmp.data(), P * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // tmp goes out of scope
     }
     // `if (width != images[0].rows || height != images[0].cols)` (src/ACMMP.cpp:766), swap included
@@ -1079,7 +1016,6 @@ int acmmp_run_patchmatch_async(acmmp_ctx *ctx) {
     if (rc) return rc;
     const acmmp_params &p = ctx->prm;
     hipStream_t s = ctx->stream;
-    ctx->depth_ok = false;  // until this run's filters are queued (a failed run leaves the strided export)
     if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev[0], s));
     ctx->cur[0] = ctx->cur[1] = 0;
     HIP_TRY(ctx, launch_init(ctx->d_kv, ctx->h_kv, state_of(ctx), s));
@@ -1094,7 +1030,9 @@ int acmmp_run_patchmatch_async(acmmp_ctx *ctx) {
     HIP_TRY(ctx, launch_finalize(ctx->d_kv, ctx->h_kv, state_of(ctx), s));
     HIP_TRY(ctx, launch_filter(ctx->d_kv, ctx->h_kv, state_of(ctx), 0, s));
     HIP_TRY(ctx, launch_filter(ctx->d_kv, ctx->h_kv, state_of(ctx), 1, s));
-    ctx->depth_ok = true;  // every pixel's depth: finalize + filters over the whole image
+    // every pixel's depth: finalize + filters over the whole image (a run that
+    // failed before this point leaves the strided export)
+    ctx->res.depth_plane_complete();
     if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev[3], s));
     ctx->prm.rng_stream += 1u;  // a further RunPatchMatch re-seeds (clock64() in the reference)
     ctx->have_state = true;
@@ -1145,8 +1083,9 @@ int acmmp_run_patchmatch_band(acmmp_ctx *ctx, int row_lo, int row_hi, acmmp_band
     if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev[2], s));
     // CheckerboardFilter reads +-5 rows (src/ACMMP.cu:1214-1328): depth /
     // normal conversion on the band +-10 rows (valid halos), the black filter
-    // on the band +-5 rows (what the red filter reads), the red one on the band
-    ctx->depth_ok = false;  // rows outside the band keep older depths
+    // on the band +-5 rows (what the red filter reads), the red one on the
+    // band. Rows outside the band keep older depths: the depth plane is not
+    // declared complete.
     HIP_TRY(ctx, launch_finalize(ctx->d_kv, ctx->h_kv, state_of(ctx, std::max(0, row_lo - 10), std::min(H, row_hi + 10)), s));
     HIP_TRY(ctx, launch_filter(ctx->d_kv, ctx->h_kv, state_of(ctx, std::max(0, row_lo - 5), std::min(H, row_hi + 5)), 0, s));
     HIP_TRY(ctx, launch_filter(ctx->d_kv, ctx->h_kv, state_of(ctx, row_lo, row_hi), 1, s));
@@ -1181,7 +1120,7 @@ int acmmp_get_plane_hypotheses(acmmp_ctx *ctx, float *planes4, size_t n) {
     if (rc) return rc;
     const size_t P = (size_t)ctx->W * ctx->H;
     if (!planes4 || n < P) return set_err(ctx, ACMMP_ERR_ARG, "output capacity %zu < %zu", n, P);
-    HIP_TRY(ctx, hipMemcpyAsync(planes4, ctx->d_rm_plane, P * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(planes4, ctx->res.planes(), P * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return ACMMP_OK;
 }
@@ -1191,7 +1130,7 @@ int acmmp_get_costs(acmmp_ctx *ctx, float *costs, size_t n) {
     if (rc) return rc;
     const size_t P = (size_t)ctx->W * ctx->H;
     if (!costs || n < P) return set_err(ctx, ACMMP_ERR_ARG, "output capacity %zu < %zu", n, P);
-    HIP_TRY(ctx, hipMemcpyAsync(costs, ctx->d_rm_cost, P * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(costs, ctx->res.costs(), P * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return ACMMP_OK;
 }
@@ -1201,7 +1140,7 @@ int acmmp_get_selected_views(acmmp_ctx *ctx, uint32_t *views, size_t n) {
     if (rc) return rc;
     const size_t P = (size_t)ctx->W * ctx->H;
     if (!views || n < P) return set_err(ctx, ACMMP_ERR_ARG, "output capacity %zu < %zu", n, P);
-    HIP_TRY(ctx, hipMemcpyAsync(views, ctx->d_rm_sv, P * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(views, ctx->res.sv(), P * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return ACMMP_OK;
 }
@@ -1209,8 +1148,8 @@ int acmmp_get_selected_views(acmmp_ctx *ctx, uint32_t *views, size_t n) {
 int acmmp_get_device_results(acmmp_ctx *ctx, const float **d_planes4, const float **d_costs) {
     int rc = check_ready(ctx);
     if (rc) return rc;
-    if (d_planes4) *d_planes4 = (const float *)ctx->d_rm_plane;
-    if (d_costs) *d_costs = ctx->d_rm_cost;
+    if (d_planes4) *d_planes4 = (const float *)ctx->res.planes();
+    if (d_costs) *d_costs = ctx->res.costs();
     return ACMMP_OK;
 }
 
@@ -1225,8 +1164,8 @@ int acmmp_get_reference_image(acmmp_ctx *ctx, float *out, size_t n) {
     int rc = check_ready(ctx);
     if (rc) return rc;
     if (!out || n < (size_t)ctx->W * ctx->H) return set_err(ctx, ACMMP_ERR_ARG, "output capacity too small");
-    HIP_TRY(ctx, hipMemcpy2DAsync(out, (size_t)ctx->W * sizeof(float), ctx->img[0],
-                                  (size_t)ctx->img_pitch[0] * sizeof(float), (size_t)ctx->W * sizeof(float),
+    HIP_TRY(ctx, hipMemcpy2DAsync(out, (size_t)ctx->W * sizeof(float), ctx->img[0].p,
+                                  (size_t)ctx->img[0].pitch * sizeof(float), (size_t)ctx->W * sizeof(float),
                                   (size_t)ctx->H, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return ACMMP_OK;
@@ -1248,13 +1187,13 @@ int acmmp_eval_costs(acmmp_ctx *ctx, const float *planes4, float *out_costs, flo
     if (rc) return rc;
     const size_t P = (size_t)ctx->W * ctx->H;
     const int ns = ctx->n - 1;
-    float4 *d_pl = nullptr;
-    float *d_out = nullptr, *d_init = nullptr;
-    uint32_t *d_views = nullptr;
-    HIP_TRY(ctx, dalloc(d_pl, P));
-    if (out_costs) HIP_TRY(ctx, dalloc(d_out, P * ns));
-    if (out_init_cost) HIP_TRY(ctx, dalloc(d_init, P));
-    if (out_init_views) HIP_TRY(ctx, dalloc(d_views, P));
+    Scratch<float4> d_pl;
+    Scratch<float> d_out, d_init;
+    Scratch<uint32_t> d_views;
+    HIP_TRY(ctx, d_pl.alloc(P));
+    if (out_costs) HIP_TRY(ctx, d_out.alloc(P * ns));
+    if (out_init_cost) HIP_TRY(ctx, d_init.alloc(P));
+    if (out_init_views) HIP_TRY(ctx, d_views.alloc(P));
     HIP_TRY(ctx, hipMemcpyAsync(d_pl, planes4, P * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, launch_eval_costs(ctx->d_kv, ctx->h_kv, d_pl, d_out, d_init, d_views, ctx->stream));
     if (out_costs)
@@ -1264,10 +1203,6 @@ int acmmp_eval_costs(acmmp_ctx *ctx, const float *planes4, float *out_costs, flo
     if (out_init_views)
         HIP_TRY(ctx, hipMemcpyAsync(out_init_views, d_views, P * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    dfree(d_pl);
-    dfree(d_out);
-    dfree(d_init);
-    dfree(d_views);
     return ACMMP_OK;
 }
 
@@ -1281,93 +1216,80 @@ int acmmp_eval_geom_costs(acmmp_ctx *ctx, const float *planes4, float *out) {
     if (rc) return rc;
     const size_t P = (size_t)ctx->W * ctx->H;
     const int ns = ctx->n - 1;
-    float4 *d_pl = nullptr;
-    float *d_out = nullptr;
-    HIP_TRY(ctx, dalloc(d_pl, P));
-    HIP_TRY(ctx, dalloc(d_out, P * ns));
+    Scratch<float4> d_pl;
+    Scratch<float> d_out;
+    HIP_TRY(ctx, d_pl.alloc(P));
+    HIP_TRY(ctx, d_out.alloc(P * ns));
     HIP_TRY(ctx, hipMemcpyAsync(d_pl, planes4, P * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, launch_eval_geom(ctx->d_kv, ctx->h_kv, d_pl, d_out, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(out, d_out, P * ns * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    dfree(d_pl);
-    dfree(d_out);
     return ACMMP_OK;
 }
 
-int acmmp_joint_bilateral_upsample(int device, const float *image, int width, int height, const float *depth,
-                                   int depth_width, int depth_height, float *out, int *image_scale) {
+namespace {
+// RunJBU (src/ACMMP.cpp:1012-1021) for host arrays (uploaded, the result
+// downloaded) or device arrays (device_src: read and written in place).
+int jbu_impl(int device, const float *image, int width, int height, const float *depth, int depth_width,
+             int depth_height, float *out, int *image_scale, bool device_src) {
     if (!image || !depth || !out || width <= 0 || height <= 0 || depth_width <= 0 || depth_height <= 0)
         return ACMMP_ERR_ARG;
-    // RunJBU (src/ACMMP.cpp:1012-1021): Imagescale from integer size ratios;
-    // 1 means nothing to upsample and the reference writes nothing.
+    // Imagescale from integer size ratios; 1 means nothing to upsample and
+    // the reference writes nothing.
     const int isc = std::max(height / depth_height, width / depth_width);
     if (image_scale) *image_scale = isc;
     if (isc <= 1) return ACMMP_OK;
     if (isc > 64) return ACMMP_ERR_UNSUPPORTED;
-    if (hipSetDevice(device) != hipSuccess) return ACMMP_ERR_HIP;
+    HIP_TRY(nullptr, hipSetDevice(device));
     const size_t P = (size_t)width * height, S = (size_t)depth_width * depth_height;
-    float *d_img = nullptr, *d_dep = nullptr, *d_out = nullptr;
     // the stream and blocks come from the engines' caches and return there
     // once the stream is synchronised (hipFree would synchronise the device)
-    hipStream_t s = nullptr;
-    hipError_t e = stream_take(device, &s);
-    if (e == hipSuccess) e = dalloc(d_img, P);
-    if (e == hipSuccess) e = dalloc(d_dep, S);
-    if (e == hipSuccess) e = dalloc(d_out, P);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_img, image, P * sizeof(float), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_dep, depth, S * sizeof(float), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = launch_jbu(d_img, width, height, d_dep, depth_width, depth_height, isc, d_out, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, P * sizeof(float), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e == hipSuccess) {
-        dfree_synced(d_img);
-        dfree_synced(d_dep);
-        dfree_synced(d_out);
-        stream_give(device, s);
-    } else {  // a failed stream may still hold work: the plain frees
-        dfree(d_img);
-        dfree(d_dep);
-        dfree(d_out);
-        if (s) (void)hipStreamDestroy(s);
+    TakenStream s;
+    Scratch<float> d_img, d_dep, d_out;
+    HIP_TRY(nullptr, s.take(device));
+    if (!device_src) {
+        HIP_TRY(nullptr, d_img.alloc(P));
+        HIP_TRY(nullptr, d_dep.alloc(S));
+        HIP_TRY(nullptr, d_out.alloc(P));
+        HIP_TRY(nullptr, hipMemcpyAsync(d_img, image, P * sizeof(float), hipMemcpyHostToDevice, s.s));
+        HIP_TRY(nullptr, hipMemcpyAsync(d_dep, depth, S * sizeof(float), hipMemcpyHostToDevice, s.s));
     }
-    return e == hipSuccess ? ACMMP_OK : ACMMP_ERR_HIP;
+    HIP_TRY(nullptr, launch_jbu(device_src ? image : d_img, width, height, device_src ? depth : d_dep, depth_width,
+                                depth_height, isc, device_src ? out : d_out, s.s));
+    if (!device_src) HIP_TRY(nullptr, hipMemcpyAsync(out, d_out, P * sizeof(float), hipMemcpyDeviceToHost, s.s));
+    HIP_TRY(nullptr, hipStreamSynchronize(s.s));
+    d_img.release_synced();
+    d_dep.release_synced();
+    d_out.release_synced();
+    s.give();
+    return ACMMP_OK;
+}
+}  // namespace
+
+int acmmp_joint_bilateral_upsample(int device, const float *image, int width, int height, const float *depth,
+                                   int depth_width, int depth_height, float *out, int *image_scale) {
+    return jbu_impl(device, image, width, height, depth, depth_width, depth_height, out, image_scale, false);
 }
 
 int acmmp_joint_bilateral_upsample_device(int device, const float *d_image, int width, int height,
                                           const float *d_depth, int depth_width, int depth_height, float *d_out,
                                           int *image_scale) {
-    if (!d_image || !d_depth || !d_out || width <= 0 || height <= 0 || depth_width <= 0 || depth_height <= 0)
-        return ACMMP_ERR_ARG;
-    const int isc = std::max(height / depth_height, width / depth_width);  // RunJBU (src/ACMMP.cpp:1012-1021)
-    if (image_scale) *image_scale = isc;
-    if (isc <= 1) return ACMMP_OK;
-    if (isc > 64) return ACMMP_ERR_UNSUPPORTED;
-    if (hipSetDevice(device) != hipSuccess) return ACMMP_ERR_HIP;
-    hipStream_t s = nullptr;
-    hipError_t e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
-    if (e == hipSuccess) e = launch_jbu(d_image, width, height, d_depth, depth_width, depth_height, isc, d_out, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (s) (void)hipStreamDestroy(s);
-    return e == hipSuccess ? ACMMP_OK : ACMMP_ERR_HIP;
+    return jbu_impl(device, d_image, width, height, d_depth, depth_width, depth_height, d_out, image_scale, true);
 }
 
 int acmmp_selftest_reciprocal(int device, uint64_t *mismatches, uint64_t *checked) {
     if (!mismatches || !checked) return ACMMP_ERR_ARG;
-    if (hipSetDevice(device) != hipSuccess) return ACMMP_ERR_HIP;
-    unsigned long long *d = nullptr;
-    if (hipMalloc((void **)&d, 2 * sizeof(unsigned long long)) != hipSuccess) return ACMMP_ERR_HIP;
-    int rc = ACMMP_OK;
-    if (hipMemset(d, 0, 2 * sizeof(unsigned long long)) != hipSuccess ||
-        launch_selftest_rcp(d, d + 1, nullptr) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
-        rc = ACMMP_ERR_HIP;
-    } else {
-        unsigned long long h[2] = {0, 0};
-        if (hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) rc = ACMMP_ERR_HIP;
-        *mismatches = h[0];
-        *checked = h[1];
-    }
-    (void)hipFree(d);
-    return rc;
+    HIP_TRY(nullptr, hipSetDevice(device));
+    Scratch<unsigned long long> d;
+    HIP_TRY(nullptr, d.alloc(2));
+    HIP_TRY(nullptr, hipMemset(d, 0, 2 * sizeof(unsigned long long)));
+    HIP_TRY(nullptr, launch_selftest_rcp(d, d + 1, nullptr));
+    HIP_TRY(nullptr, hipDeviceSynchronize());
+    unsigned long long h[2] = {0, 0};
+    HIP_TRY(nullptr, hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost));
+    *mismatches = h[0];
+    *checked = h[1];
+    return ACMMP_OK;
 }
 
 int acmmp_set_timing(acmmp_ctx *ctx, int enable) {

@@ -217,18 +217,15 @@ int acmmp_get_support_points(acmmp_ctx *ctx, int32_t *xy, int capacity, int *cou
     const int W = ctx->W, H = ctx->H;
     const int nbc = (W + kSupportStep - 1) / kSupportStep, nbr = (H + kSupportStep - 1) / kSupportStep;
     const int nblocks = nbc * nbr;
-    int32_t *d_out = nullptr;
+    Scratch<int32_t> d_out;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, dalloc(d_out, (size_t)nblocks));
-    k_support_points<<<(nblocks + 255) / 256, 256, 0, ctx->stream>>>(ctx->d_rm_cost, W, H, nbr, nblocks, d_out);
+    HIP_TRY(ctx, d_out.alloc((size_t)nblocks));
+    k_support_points<<<(nblocks + 255) / 256, 256, 0, ctx->stream>>>(ctx->res.costs(), W, H, nbr, nblocks, d_out);
+    HIP_TRY(ctx, hipGetLastError());
     std::vector<int32_t> h(nblocks);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(h.data(), d_out, nblocks * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e == hipSuccess) dfree_synced(d_out);
-    else dfree(d_out);
-    HIP_TRY(ctx, e);
+    HIP_TRY(ctx, hipMemcpyAsync(h.data(), d_out, nblocks * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    d_out.release_synced();
     int n = 0;
     for (int b = 0; b < nblocks; ++b) {
         if (h[b] < 0) continue;
@@ -265,12 +262,12 @@ int acmmp_build_planar_prior(acmmp_ctx *ctx, const int32_t *tris, int ntris, flo
     }
     const int nt = (int)(kept.size() / 6);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int32_t *d_tris = nullptr;
-    float4 *d_planes = nullptr;
-    int *d_overflow = nullptr;
-    HIP_TRY(ctx, dalloc(d_tris, kept.size() + 6));
-    HIP_TRY(ctx, dalloc(d_planes, (size_t)nt + 1));
-    HIP_TRY(ctx, dalloc(d_overflow, 1));
+    Scratch<int32_t> d_tris;
+    Scratch<float4> d_planes;
+    Scratch<int> d_overflow;
+    HIP_TRY(ctx, d_tris.alloc(kept.size() + 6));
+    HIP_TRY(ctx, d_planes.alloc((size_t)nt + 1));
+    HIP_TRY(ctx, d_overflow.alloc(1));
     HIP_TRY(ctx, dalloc(ctx->d_prior, P));
     HIP_TRY(ctx, dalloc(ctx->d_mask, P));
     hipStream_t s = ctx->stream;
@@ -278,7 +275,7 @@ int acmmp_build_planar_prior(acmmp_ctx *ctx, const int32_t *tris, int ntris, flo
     HIP_TRY(ctx, hipMemsetAsync(d_overflow, 0, sizeof(int), s));
     if (nt > 0) {
         HIP_TRY(ctx, hipMemcpyAsync(d_tris, kept.data(), kept.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        k_prior_planes<<<(nt + 127) / 128, 128, 0, s>>>(ctx->d_rm_plane, W, ctx->cams[0], d_tris, nt, d_planes);
+        k_prior_planes<<<(nt + 127) / 128, 128, 0, s>>>(ctx->res.planes(), W, ctx->cams[0], d_tris, nt, d_planes);
         HIP_TRY(ctx, hipGetLastError());
         k_raster_triangles<<<nt, 256, 0, s>>>(d_tris, nt, W, H, ctx->d_mask, d_overflow);
         HIP_TRY(ctx, hipGetLastError());
@@ -292,9 +289,9 @@ int acmmp_build_planar_prior(acmmp_ctx *ctx, const int32_t *tris, int ntris, flo
         HIP_TRY(ctx, hipMemcpyAsync(out_planes4, d_planes, (size_t)nt * sizeof(float4), hipMemcpyDeviceToHost, s));
     if (out_mask) HIP_TRY(ctx, hipMemcpyAsync(out_mask, ctx->d_mask, P * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(ctx, hipStreamSynchronize(s));
-    dfree_synced(d_tris);
-    dfree_synced(d_planes);
-    dfree_synced(d_overflow);
+    d_tris.release_synced();
+    d_planes.release_synced();
+    d_overflow.release_synced();
     if (overflow) return set_err(ctx, ACMMP_ERR_UNSUPPORTED, "%d triangles longer than %d px", overflow, kMaxSeq);
     ctx->have_prior = true;
     return ACMMP_OK;

@@ -170,7 +170,7 @@ class ResidentViews:
         by_tensor = {}
         self.textures = {}
         for i, im in images.items():
-            key = (im.data_ptr(), tuple(im.shape))
+            key = (im.data_ptr(), tuple(im.shape), tuple(im.stride()), im.dtype)
             if key not in by_tensor:
                 by_tensor[key] = Texture.of(im, pool.device)
             self.textures[i] = by_tensor[key]
