@@ -30,6 +30,9 @@ import pytest
 import oracle
 from acmmp_amd import default_params
 from acmmp_amd.engine import make_camera
+# the float64 restatements of the reference device code (test-local, independent
+# of the C oracle) live in ref64.py, shared with the general-rig tests
+from ref64 import ref_geom_cost, ref_homography, ref_ncc
 
 # fp32 oracle vs fp64 restatement: NCC costs live in [0, 2]; the fp32 sums of
 # 36 weighted samples of 0..255 intensities carry ~1e-6 relative error, which
@@ -42,13 +45,6 @@ def _cam(f=100.0, cx=32.0, cy=24.0, R=None, t=(0, 0, 0), w=64, h=48, dmin=1.0, d
     K = np.array([[f, 0, cx], [0, f, cy], [0, 0, 1]], np.float64)
     R = np.eye(3) if R is None else np.asarray(R, np.float64)
     return make_camera(K, R, np.asarray(t, np.float64), w, h, dmin, dmax)
-
-
-def _np(cam):
-    K = np.array(cam.K[:], np.float64).reshape(3, 3)
-    R = np.array(cam.R[:], np.float64).reshape(3, 3)
-    t = np.array(cam.t[:], np.float64)
-    return K, R, t
 
 
 def _texture(h, w, seed):
@@ -67,114 +63,6 @@ def _rot(ax, ay, az):
     Ry = np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]])
     Rz = np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1]])
     return Rz @ Ry @ Rx
-
-
-# ---------------------------------------------------------------------------
-# float64 restatement of the reference device code (test-local, independent of
-# the C oracle).
-
-def ref_homography(rc, sc, plane):
-    """ComputeHomography, src/ACMMP.cu:262-322."""
-    Kr, Rr, tr = _np(rc)
-    Ks, Rs, ts = _np(sc)
-    Cr = -Rr.T @ tr
-    Cs = -Rs.T @ ts
-    Rrel = Rs @ Rr.T
-    trel = Rs @ (Cr - Cs)
-    n = np.asarray(plane[:3], np.float64)
-    H = Rrel - np.outer(trel, n) / plane[3]
-    tmp = np.empty((3, 3))
-    for r in range(3):
-        tmp[r, 0] = H[r, 0] / Kr[0, 0]
-        tmp[r, 1] = H[r, 1] / Kr[1, 1]
-        tmp[r, 2] = -H[r, 0] * Kr[0, 2] / Kr[0, 0] - H[r, 1] * Kr[1, 2] / Kr[1, 1] + H[r, 2]
-    out = np.empty((3, 3))
-    out[0] = Ks[0, 0] * tmp[0] + Ks[0, 2] * tmp[2]
-    out[1] = Ks[1, 1] * tmp[1] + Ks[1, 2] * tmp[2]
-    out[2] = Ks[2, 2] * tmp[2]
-    return out
-
-
-def _tex_bilinear(img, x, y):
-    """tex2D linear filtering with clamp-to-edge at (x, y) in texel-centre
-    coordinates as passed by the reference (pt + 0.5)."""
-    h, w = img.shape
-    xs, ys = x - 0.5, y - 0.5
-    x0, y0 = math.floor(xs), math.floor(ys)
-    a, b = xs - x0, ys - y0
-
-    def t(r, c):
-        return float(img[min(max(r, 0), h - 1), min(max(c, 0), w - 1)])
-
-    top = (1 - a) * t(y0, x0) + a * t(y0, x0 + 1)
-    bot = (1 - a) * t(y0 + 1, x0) + a * t(y0 + 1, x0 + 1)
-    return (1 - b) * top + b * bot
-
-
-def ref_ncc(prm, rc, sc, rimg, simg, px, py, plane):
-    """ComputeBilateralNCC, src/ACMMP.cu:360-432 (float64)."""
-    H = ref_homography(rc, sc, plane)
-
-    def corr(x, y):
-        v = H @ np.array([x, y, 1.0])
-        return v[0] / v[2], v[1] / v[2]
-
-    cx, cy = corr(px, py)
-    if cx >= sc.width or cx < 0 or cy >= sc.height or cy < 0:
-        return 2.0
-    radius = prm.patch_size // 2
-    centre = float(rimg[py, px])
-    sr = srr = ss = sss = srs = sw = 0.0
-    for i in range(-radius, radius + 1, prm.radius_increment):
-        for j in range(-radius, radius + 1, prm.radius_increment):
-            rx, ry = px + i, py + j
-            r = _tex_bilinear(rimg, rx + 0.5, ry + 0.5)
-            ux, uy = corr(rx, ry)
-            s = _tex_bilinear(simg, ux + 0.5, uy + 0.5)
-            wgt = math.exp(-math.sqrt(i * i + j * j) / (2 * prm.sigma_spatial ** 2)
-                           - abs(r - centre) / (2 * prm.sigma_color ** 2))
-            sr += wgt * r
-            srr += wgt * r * r
-            ss += wgt * s
-            sss += wgt * s * s
-            srs += wgt * r * s
-            sw += wgt
-    sr, srr, ss, sss, srs = (v / sw for v in (sr, srr, ss, sss, srs))
-    vr, vs = srr - sr * sr, sss - ss * ss
-    if vr < 1e-5 or vs < 1e-5:
-        return 2.0
-    return max(0.0, min(2.0, 1.0 - (srs - sr * ss) / math.sqrt(vr * vs)))
-
-
-def ref_geom_cost(rc, sc, src_depth, plane, px, py):
-    """ComputeGeomConsistencyCost, src/ACMMP.cu:518-543 (float64)."""
-    Kr, Rr, tr = _np(rc)
-    Ks, Rs, ts = _np(sc)
-    # ComputeDepthfromPlaneHypothesis (src/ACMMP.cu:163-168)
-    n = plane[:3]
-    depth = -plane[3] * Kr[0, 0] / ((px - Kr[0, 2]) * n[0] + (Kr[0, 0] / Kr[1, 1]) * (py - Kr[1, 2]) * n[1]
-                                     + Kr[0, 0] * n[2])
-
-    def to_world(K, R, t, x, y, d):
-        X = np.array([d * (x - K[0, 2]) / K[0, 0], d * (y - K[1, 2]) / K[1, 1], d])
-        return R.T @ X - R.T @ t
-
-    def project(K, R, t, X):
-        c = R @ X + t
-        d = K[2] @ c
-        return (K[0] @ c) / d, (K[1] @ c) / d
-
-    X = to_world(Kr, Rr, tr, px, py, depth)
-    sx, sy = project(Ks, Rs, ts, X)
-    hh, ww = src_depth.shape
-    ix = min(max(int(sx), 0), ww - 1)
-    iy = min(max(int(sy), 0), hh - 1)
-    d = float(src_depth[iy, ix])
-    if d == 0.0:
-        return 3.0
-    Y = to_world(Ks, Rs, ts, sx, sy, d)
-    bx, by = project(Kr, Rr, tr, Y)
-    return min(3.0, math.hypot(px - bx, py - by))
 
 
 # ---------------------------------------------------------------------------
