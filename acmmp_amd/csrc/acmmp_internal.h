@@ -1,5 +1,6 @@
 // acmmp_internal.h — device-side data layout shared by the kernels
-// (acmmp_kernels.hip) and the host engine (acmmp_engine.hip).
+// (acmmp_kernels.hip, acmmp_kernels_tx.hip, through acmmp_dev.h) and the host
+// engine (acmmp_engine.hip).
 //
 // HBM layout (per engine = per reference view being processed):
 //   * source images: one pitched fp32 buffer per view (pitch = width rounded

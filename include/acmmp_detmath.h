@@ -15,7 +15,7 @@
  * This header is math-library plumbing (the stand-in for libm/CUDA intrinsics),
  * not part of the PatchMatch algorithm; the algorithm itself is written twice,
  * independently: oracle/acmmp_oracle.c (literal restatement) and
- * acmmp_amd/csrc/acmmp_kernels.hip (MI355X kernels).
+ * acmmp_amd/csrc/acmmp_kernels*.hip with acmmp_dev.h (MI355X kernels).
  *
  * Accuracy: expf/sinf/cosf/acosf within ~2 ulp of the correctly rounded value
  * over the ranges PatchMatch uses (checked in tests/test_detmath.py against

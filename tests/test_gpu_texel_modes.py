@@ -1,4 +1,4 @@
-"""Texel storage of the gather kernels (acmmp_kernels.hip, TX template bits),
+"""Texel storage of the gather kernels (acmmp_dev.h, TX template bits),
 the most compact form every view fits: u8 quads (4 B per bilinear footprint)
 when every view is integer-valued in [0, 255], else f16 difference quads
 (8 B) when every stored value (texels and the fp32 row differences) is exact

@@ -1,7 +1,7 @@
 """Views of 2^24 padded records or more (ETH3D high-res at native size,
 BASELINE cfg5: 6048x4032): the gather kernels then form the record index with
 an integer 24x24-bit multiply-add instead of the exact-fp32 form
-(acmmp_kernels.hip, ncc_sums_rows<FAST, WIDE>).
+(acmmp_dev.h, ncc_sums_rows<FAST, WIDE>).
 
   * ACMMP_WIDE_INDEX=1 forces that path at oracle-sized inputs, so it is held
     to the same bit-exact parity as the default path (T1 cost vectors, T3

@@ -1,5 +1,5 @@
-"""ISA guards for k_sweep (CPU tier: hipcc cross-compiles the NS 9, u8-quad
-instantiation to a gfx950 listing, as `make resource-dev` does). They pin the
+"""ISA guards for k_sweep (CPU tier: hipcc cross-compiles the shipped u8-quad
+unit to a gfx950 listing, as `make resource` does). They pin the
 round-4 latency fixes, which change no result and so no parity test would
 notice losing them:
 - no generic (flat) loads: a flat load also counts against lgkmcnt, so every
@@ -32,8 +32,8 @@ pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not ins
 def listing(tmp_path_factory):
     out = tmp_path_factory.mktemp("isa") / "dev_kernels.s"
     cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
-           "-fno-slp-vectorize", "-I../../include", "-DACMMP_DEV_SUBSET", "-DACMMP_DEV_ALL_NS", "--cuda-device-only", "-S",
-           "acmmp_kernels.hip", "-o", str(out), "-Rpass-analysis=kernel-resource-usage"]
+           "-fno-slp-vectorize", "-I../../include", "-DACMMP_TX_UNIT=2", "--cuda-device-only", "-S",
+           "acmmp_kernels_tx.hip", "-o", str(out), "-Rpass-analysis=kernel-resource-usage"]
     r = subprocess.run(cmd, cwd=CSRC, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     text = out.read_text()
