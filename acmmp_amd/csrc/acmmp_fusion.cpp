@@ -41,9 +41,14 @@
 #include <vector>
 
 #include "../../include/acmmp.h"
+#include "acmmp_dense.h"
 #include "acmmp_hostio.h"
 
 namespace {
+
+using acmmp_dense::camera_path;
+using acmmp_dense::id8;
+using acmmp_dense::result_folder;
 
 thread_local std::string f_err;
 
@@ -55,12 +60,6 @@ int ffail(int code, const char *fmt, ...) {
     va_end(ap);
     f_err = buf;
     return code;
-}
-
-std::string id8(int id) {
-    char b[32];
-    std::snprintf(b, sizeof(b), "%08d", id);
-    return b;
 }
 
 struct F3 {
@@ -301,7 +300,8 @@ struct MaskBits {
 };
 
 // Runs fn(0..n-1) on the pool's workers (the caller waits); returns the
-// status of the lowest failing index with its message, as parallel_for does.
+// status of the lowest failing index with its message (what the sequential
+// loop reports first).
 template <class Fn>
 int pool_for(Pool &pool, int n, Fn fn) {
     std::vector<int> rc((size_t)std::max(n, 0), ACMMP_OK);
@@ -310,32 +310,6 @@ int pool_for(Pool &pool, int n, Fn fn) {
         rc[(size_t)i] = fn(i);
         if (rc[(size_t)i]) msg[(size_t)i] = f_err;
     }));
-    for (int i = 0; i < n; ++i)
-        if (rc[(size_t)i]) {
-            f_err = msg[(size_t)i];
-            return rc[(size_t)i];
-        }
-    return ACMMP_OK;
-}
-
-// Runs fn(0..n-1) on acmmp_host_threads() threads; returns the status of the lowest
-// failing index with its message (what the sequential loop reports first).
-template <class Fn>
-int parallel_for(int n, Fn fn) {
-    const int workers = std::min<int>(n, acmmp_host_threads());
-    std::vector<int> rc((size_t)std::max(n, 0), ACMMP_OK);
-    std::vector<std::string> msg(rc.size());
-    std::atomic<int> next{0};
-    auto work = [&]() {
-        for (int i; (i = next.fetch_add(1)) < n;) {
-            rc[(size_t)i] = fn(i);
-            if (rc[(size_t)i]) msg[(size_t)i] = f_err;
-        }
-    };
-    std::vector<std::thread> pool;
-    for (int t = 1; t < workers; ++t) pool.emplace_back(work);
-    work();
-    for (auto &t : pool) t.join();
     for (int i = 0; i < n; ++i)
         if (rc[(size_t)i]) {
             f_err = msg[(size_t)i];
@@ -546,7 +520,6 @@ int acmmp_run_fusion(const char *dense_folder, const char *output_folder, const 
     if (!dense_folder || !output_folder || !problems || count <= 0) return ffail(ACMMP_ERR_ARG, "bad args");
     const std::string dense = dense_folder, out = output_folder;
     const std::string image_folder = dense + (image_dir ? image_dir : "/images");
-    const std::string cam_folder = dense + "/cams";
     const bool use_masks = mask_folder && std::string(mask_folder) != " " && mask_folder[0] != 0;
     const size_t n = (size_t)count;
     std::vector<std::vector<uint8_t>> images(n);
@@ -581,9 +554,9 @@ int acmmp_run_fusion(const char *dense_folder, const char *output_folder, const 
         std::vector<uint8_t> img;
         int rc = acmmp_internal_read_image_bgr(ipath.c_str(), img, iw, ih);
         if (rc) return ffail(rc, "cannot read image %s", ipath.c_str());
-        const std::string cpath = cam_folder + "/" + id8(id) + "_cam.txt";
+        const std::string cpath = camera_path(dense, id);
         if (acmmp_read_camera(cpath.c_str(), &cameras[i])) return ffail(ACMMP_ERR_IO, "cannot read %s", cpath.c_str());
-        const std::string rf = out + "/2333_" + id8(id);
+        const std::string rf = result_folder(out, id);
         int h, w, nb, h2, w2, nb2;
         rc = read_dmb(rf + (geom_consistency ? "/depths_geom.dmb" : "/depths.dmb"), depths[i], h, w, nb);
         if (!rc) rc = read_dmb(rf + "/normals.dmb", normals[i], h2, w2, nb2);
@@ -959,11 +932,11 @@ int acmmp_run_prior_aware_fusion(const char *dense_folder, const char *output_fo
         std::vector<uint8_t> img;
         int rc = acmmp_internal_read_image_bgr(ipath.c_str(), img, iw, ih);
         if (rc) return ffail(rc, "cannot read image %s", ipath.c_str());
-        const std::string cpath = dense + "/cams/" + id8(id) + "_cam.txt";
+        const std::string cpath = camera_path(dense, id);
         if (acmmp_read_camera(cpath.c_str(), &in.cameras[i]))
             return ffail(ACMMP_ERR_IO, "cannot read %s", cpath.c_str());
         // maps of the other reconstruction (fusion_folder) and of this run's (output_folder) priors
-        const std::string rf = fus + "/2333_" + id8(id), pf = out + "/2333_" + id8(id);
+        const std::string rf = result_folder(fus, id), pf = result_folder(out, id);
         int h, w, nb, h2, w2, nb2, h3, w3, nb3, h4, w4, nb4;
         rc = read_dmb(rf + suffix, in.depths[i], h, w, nb);
         if (!rc) rc = read_dmb(rf + "/normals.dmb", in.normals[i], h2, w2, nb2);

@@ -11,16 +11,14 @@
 // <out>/ACMMP_prior_model.ply.
 #include <sys/stat.h>
 
-#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <atomic>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "../../include/acmmp.h"
+#include "acmmp_dense.h"
 #include "acmmp_vp.h"
 
 namespace {
@@ -182,34 +180,13 @@ int main(int argc, char **argv) {
     opt.verbose = quiet ? 0 : 1;
     unsigned pass = 0;
     std::string pass_error;  // the first failing view's message (set by for_views)
-    // fn(0..num_images-1), `lanes` views at a time; false (and pass_error =
-    // the lowest failing view's message, what the one-at-a-time loop reports)
-    // if any fails
+    // fn(0..num_images-1), `lanes` views at a time, none started after a
+    // failure; false (and pass_error = the lowest failing view's message, what
+    // the one-at-a-time loop reports) if any fails
     auto for_views = [&](int lanes, auto fn) -> bool {
-        lanes = std::max(1, std::min(lanes, num_images));
-        std::vector<int> rc((size_t)num_images, 0);
-        std::vector<std::string> msg((size_t)num_images);
-        std::atomic<int> next{0};
-        std::atomic<bool> failed{false};
-        auto worker = [&] {
-            for (int i; !failed.load() && (i = next.fetch_add(1)) < num_images;) {
-                rc[(size_t)i] = fn(i);
-                if (rc[(size_t)i]) {
-                    msg[(size_t)i] = acmmp_pipeline_last_error();
-                    failed = true;
-                }
-            }
-        };
-        std::vector<std::thread> pool;
-        for (int t = 1; t < lanes; ++t) pool.emplace_back(worker);
-        worker();
-        for (auto &t : pool) t.join();
-        for (int i = 0; i < num_images; ++i)
-            if (rc[(size_t)i]) {
-                pass_error = msg[(size_t)i];
-                return false;
-            }
-        return true;
+        return acmmp_dense::parallel_index(
+                   num_images, lanes, fn, [](int) { return std::string(acmmp_pipeline_last_error()); }, pass_error,
+                   /*stop_on_first_error=*/true) == ACMMP_OK;
     };
     auto run_pass = [&](bool geom, bool planar, bool hier, bool multi, bool seeded = false) -> bool {
         opt.seeded = seeded;
@@ -269,12 +246,7 @@ int main(int argc, char **argv) {
     int flag = 0;
     while (max_num_downscale >= 0) {  // src/main_ACMMP.cpp:96-176
         if (!quiet) std::printf("Scale: %d\n", max_num_downscale);
-        for (auto &p : problems) {
-            if (p.num_downscale >= 0) {
-                p.cur_image_size = (int)(p.max_image_size / std::pow(2, p.num_downscale));
-                p.num_downscale--;
-            }
-        }
+        acmmp_dense::scale_step(problems.data(), num_images);
         if (flag == 0) {
             flag = 1;
             if (!run_pass(false, true, false, false, prior)) return die_pass("ProcessProblem");

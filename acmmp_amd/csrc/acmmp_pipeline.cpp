@@ -16,7 +16,6 @@
 #include <zlib.h>
 
 #include <algorithm>
-#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
@@ -32,9 +31,12 @@
 #include <vector>
 
 #include "../../include/acmmp.hpp"
+#include "acmmp_dense.h"
 #include "acmmp_hostio.h"
 
 namespace {
+
+using namespace acmmp_dense;
 
 thread_local std::string g_err;
 
@@ -46,26 +48,6 @@ int fail(int code, const char *fmt, ...) {
     va_end(ap);
     g_err = buf;
     return code;
-}
-
-std::string id8(int id) {
-    char b[32];
-    std::snprintf(b, sizeof(b), "%08d", id);
-    return b;
-}
-
-bool exists(const std::string &p) {
-    struct stat st;
-    return ::stat(p.c_str(), &st) == 0;
-}
-
-std::string result_folder(const std::string &out, int ref_id) { return out + "/2333_" + id8(ref_id); }
-
-std::string image_path(const std::string &dense, int id) {
-    const std::string base = dense + "/images/" + id8(id);
-    for (const char *ext : {".jpg", ".pgm", ".pfm"})
-        if (exists(base + ext)) return base + ext;
-    return base + ".jpg";
 }
 
 // Decoded-image cache. The reference re-reads and re-decodes every image of a
@@ -153,11 +135,6 @@ int read_dmb(const std::string &path, std::vector<float> &data, int &h, int &w, 
     return ACMMP_OK;
 }
 
-int write_dmb(const std::string &path, int h, int w, int nb, const float *data) {
-    if (acmmp_write_dmb(path.c_str(), h, w, nb, data)) return fail(ACMMP_ERR_IO, "cannot write %s", path.c_str());
-    return ACMMP_OK;
-}
-
 // ---- triangulation.png (src/acmmp_definitions.cpp:310-330): the reference
 // image as BGR with the triangle edges drawn in red, 1-px 8-connected lines.
 int write_png8(const std::string &path, int w, int h, int channels, const uint8_t *px) {
@@ -216,31 +193,11 @@ void triangulation_picture(acmmp::ACMMP &acmmp, std::vector<uint8_t> &rgb, std::
     }
 }
 
-// Runs fn(0..n-1) on acmmp_host_threads() threads. Returns the status of the lowest
-// failing index and leaves its message in this thread's error slot, so the
-// caller sees what the sequential loop would have reported first.
+// fn(0..n-1) on the library's host threads; the lowest failing index's
+// status, its message in this thread's error slot
 template <class Fn>
 int parallel_views(int n, Fn fn) {
-    const int workers = std::min<int>(n, acmmp_host_threads());
-    std::vector<int> rc((size_t)n, ACMMP_OK);
-    std::vector<std::string> msg((size_t)n);
-    std::atomic<int> next{0};
-    auto work = [&]() {
-        for (int i; (i = next.fetch_add(1)) < n;) {
-            rc[(size_t)i] = fn(i);
-            if (rc[(size_t)i]) msg[(size_t)i] = g_err;
-        }
-    };
-    std::vector<std::thread> pool;
-    for (int t = 1; t < workers; ++t) pool.emplace_back(work);
-    work();
-    for (auto &t : pool) t.join();
-    for (int i = 0; i < n; ++i)
-        if (rc[(size_t)i]) {
-            g_err = msg[(size_t)i];
-            return rc[(size_t)i];
-        }
-    return ACMMP_OK;
+    return parallel_index(n, acmmp_host_threads(), fn, [](int) { return g_err; }, g_err);
 }
 
 // One view of InputInitialization (src/ACMMP.cpp:536-598): image + camera,
@@ -248,17 +205,14 @@ int parallel_views(int n, Fn fn) {
 int load_view(const std::string &dense, int id, int max_image_size, acmmp::Image &im, acmmp_camera &cam) {
     int rc = load_image(image_path(dense, id), im);
     if (rc) return rc;
-    const std::string cam_path = dense + "/cams/" + id8(id) + "_cam.txt";
+    const std::string cam_path = camera_path(dense, id);
     rc = acmmp_read_camera(cam_path.c_str(), &cam);
     if (rc) return fail(rc, "cannot read camera %s", cam_path.c_str());
     cam.height = im.rows;
     cam.width = im.cols;
-    if (im.cols <= max_image_size && im.rows <= max_image_size) return ACMMP_OK;
-    const float factor_x = static_cast<float>(max_image_size) / im.cols;
-    const float factor_y = static_cast<float>(max_image_size) / im.rows;
-    const float factor = std::min(factor_x, factor_y);
-    const int new_cols = (int)std::round(im.cols * factor);
-    const int new_rows = (int)std::round(im.rows * factor);
+    int new_cols = 0, new_rows = 0;
+    scaled_size(im.cols, im.rows, max_image_size, &new_cols, &new_rows);
+    if (new_cols == im.cols && new_rows == im.rows) return ACMMP_OK;
     const float scale_x = new_cols / static_cast<float>(im.cols);
     const float scale_y = new_rows / static_cast<float>(im.rows);
     acmmp::Image scaled;
@@ -370,6 +324,18 @@ int acmmp_load_view(const char *dense_folder, int image_id, int max_image_size, 
     return ACMMP_OK;
 }
 
+int acmmp_view_size(const char *dense_folder, int image_id, int max_image_size, int *width, int *height) {
+    if (!dense_folder || !width || !height) return fail(ACMMP_ERR_ARG, "bad args");
+    const std::string path = image_path(dense_folder, image_id);
+    int w = 0, h = 0;
+    const int rc = acmmp_image_size(path.c_str(), &w, &h);
+    if (rc) return fail(rc, "cannot read image %s", path.c_str());
+    *width = w;
+    *height = h;
+    if (max_image_size > 0) scaled_size(w, h, max_image_size, width, height);
+    return ACMMP_OK;
+}
+
 const char *acmmp_pipeline_last_error(void) { return g_err.c_str(); }
 
 int acmmp_generate_sample_list(const char *dense_folder, acmmp_problem *problems, int capacity, int *count) {
@@ -413,10 +379,9 @@ int acmmp_compute_multiscale_settings(const char *dense_folder, acmmp_problem *p
     const int size_bound = 1000;
     int best = -1;
     for (int i = 0; i < count; ++i) {
-        const std::string path = image_path(dense_folder, problems[i].ref_image_id);
         int cols = 0, rows = 0;
-        const int rc = acmmp_image_size(path.c_str(), &cols, &rows);
-        if (rc) return fail(rc, "cannot read image %s", path.c_str());
+        const int rc = acmmp_view_size(dense_folder, problems[i].ref_image_id, 0, &cols, &rows);
+        if (rc) return rc;
         int max_size = std::max(rows, cols);
         if (max_size > pmp.max_image_size) max_size = pmp.max_image_size;
         problems[i].max_image_size = max_size;
@@ -627,19 +592,8 @@ int acmmp_process_problem(const char *dense_folder, const char *output_folder, c
         const auto &planes = acmmp.GetPlaneHypotheses();
         const auto &costs = acmmp.GetCosts();
         clk.mark("fetch");
-        const size_t P = (size_t)width * height;
-        std::vector<float> depths(P), normals(P * 3);
-        for (size_t i = 0; i < P; ++i) {
-            depths[i] = planes[i].w;
-            normals[3 * i] = planes[i].x;
-            normals[3 * i + 1] = planes[i].y;
-            normals[3 * i + 2] = planes[i].z;
-        }
-        const std::string suffix = opt->geom_consistency ? "/depths_geom.dmb" : "/depths.dmb";
-        int rc = write_dmb(folder + suffix, height, width, 1, depths.data());
-        if (!rc) rc = write_dmb(folder + "/normals.dmb", height, width, 3, normals.data());
-        if (!rc) rc = write_dmb(folder + "/costs.dmb", height, width, 1, costs.data());
-        if (rc) return rc;
+        if (write_view_maps(folder, opt->geom_consistency != 0, height, width, &planes[0].x, costs.data()))
+            return fail(ACMMP_ERR_IO, "cannot write the maps of view %d under %s", problem.ref_image_id, folder.c_str());
         clk.mark("write");
     } catch (const acmmp::Error &e) {
         return fail(e.status(), "view %d: %s", problem.ref_image_id, e.what());
@@ -661,11 +615,8 @@ int acmmp_joint_bilateral_upsampling(const char *dense_folder, const char *outpu
     acmmp::Image im;
     rc = load_image(image_path(dense_folder, problem->ref_image_id), im);
     if (rc) return rc;
-    const float factor_x = static_cast<float>(acmmp_size) / im.cols;
-    const float factor_y = static_cast<float>(acmmp_size) / im.rows;
-    const float factor = std::min(factor_x, factor_y);
-    const int new_cols = (int)std::round(im.cols * factor);
-    const int new_rows = (int)std::round(im.rows * factor);
+    int new_cols = 0, new_rows = 0;
+    rescaled_size(im.cols, im.rows, acmmp_size, &new_cols, &new_rows);  // no "<= acmmp_size" test here (:428-433)
     std::vector<float> scaled((size_t)new_cols * new_rows);
     acmmp_resize_linear(im.data.data(), im.cols, im.rows, scaled.data(), new_cols, new_rows);
     std::vector<float> out(scaled.size());
@@ -675,7 +626,10 @@ int acmmp_joint_bilateral_upsampling(const char *dense_folder, const char *outpu
     if (rc) return fail(rc, "JBU of view %d failed", problem->ref_image_id);
     if (isc <= 1) return ACMMP_OK;  // "Image.rows = Depthmap.rows": nothing written (src/ACMMP.cpp:1016-1019)
     ::mkdir(folder.c_str(), 0777);
-    return write_dmb(folder + "/depths.dmb", new_rows, new_cols, 1, out.data());
+    const std::string path = folder + "/depths.dmb";
+    if (acmmp_write_dmb(path.c_str(), new_rows, new_cols, 1, out.data()))
+        return fail(ACMMP_ERR_IO, "cannot write %s", path.c_str());
+    return ACMMP_OK;
 }
 
 }  // extern "C"

@@ -50,7 +50,6 @@
 #include <cerrno>
 #include <atomic>
 #include <chrono>
-#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -62,9 +61,12 @@
 #include <vector>
 
 #include "../../include/acmmp.h"
+#include "acmmp_dense.h"
 #include "acmmp_vp.h"
 
 namespace {
+
+using namespace acmmp_dense;
 
 struct Fail : std::runtime_error {
     using std::runtime_error::runtime_error;
@@ -322,23 +324,6 @@ struct DevBuf {
     }
 };
 
-std::string image_path(const std::string &dense, int id) {
-    char name[32];
-    std::snprintf(name, sizeof name, "%08d", id);
-    const std::string base = dense + "/images/" + name;
-    for (const char *ext : {".jpg", ".pgm", ".pfm"}) {
-        struct stat st;
-        if (::stat((base + ext).c_str(), &st) == 0) return base + ext;
-    }
-    return base + ".jpg";
-}
-
-std::string result_folder(const std::string &out, int ref_id) {
-    char name[32];
-    std::snprintf(name, sizeof name, "/2333_%08d", ref_id);
-    return out + name;
-}
-
 struct ViewState {
     DevBuf planes, costs;  // (H, W, 4) world normal + depth, (H, W)
     int W = 0, H = 0;
@@ -362,8 +347,7 @@ class Driver {
         std::vector<double> cost((size_t)n);
         for (int i = 0; i < n; ++i) {
             int w = 0, h = 0;
-            acmmp_check(acmmp_image_size(image_path(o.dense, problems_[(size_t)i].ref_image_id).c_str(), &w, &h),
-                        "image header");
+            acmmp_check(acmmp_view_size(o.dense.c_str(), problems_[(size_t)i].ref_image_id, 0, &w, &h), "image header");
             cost[(size_t)i] = (double)w * h * std::max(problems_[(size_t)i].num_src_images, 1);
         }
         std::vector<int> order((size_t)n);
@@ -414,11 +398,7 @@ class Driver {
         ::mkdir(output_folder_.c_str(), 0777);
         bool first = true;
         while (max_down_ >= 0) {
-            for (auto &p : problems_)  // cur_image_size for this scale (src/main_ACMMP.cpp:99-106)
-                if (p.num_downscale >= 0) {
-                    p.cur_image_size = (int)(p.max_image_size / std::pow(2.0, p.num_downscale));
-                    p.num_downscale--;
-                }
+            scale_step(problems_.data(), (int)problems_.size());
             {
                 Clock c(this, "load");
                 shapes();
@@ -519,35 +499,30 @@ class Driver {
         std::vector<std::vector<float>> host(owned_.size());
         std::vector<acmmp_camera> own_cams(owned_.size());
         const size_t nwork = need.size() + owned_.size();
-        std::vector<std::string> errs(nwork);
-        std::atomic<size_t> next{0};
-        auto worker = [&]() {
-            for (size_t k; (k = next++) < nwork;) {
+        auto image_id = [&](size_t k) {
+            return k < need.size() ? need[k] : problems_[(size_t)owned_[k - need.size()]].ref_image_id;
+        };
+        std::string err;
+        const int load_rc = parallel_index(
+            (int)nwork, acmmp_host_threads(),
+            [&](int i) -> int {
+                const size_t k = (size_t)i;
                 const bool pixels = k >= need.size();
-                const int v = pixels ? owned_[k - need.size()] : -1;
-                const int id = pixels ? problems_[(size_t)v].ref_image_id : need[k];
+                const int id = image_id(k);
                 acmmp_camera &cam = pixels ? own_cams[k - need.size()] : cams[k];
                 const int size = problems_[(size_t)index_of_.at(id)].cur_image_size;
-                int rc = acmmp_load_view(o_.dense.c_str(), id, size, nullptr, 0, &cam);
-                if (rc != ACMMP_OK && rc != ACMMP_ERR_ARG) {
-                    errs[k] = std::string("acmmp_load_view: ") + acmmp_pipeline_last_error();
-                    continue;
-                }
-                if (!pixels) continue;
+                const int rc = acmmp_load_view(o_.dense.c_str(), id, size, nullptr, 0, &cam);
+                if (rc != ACMMP_OK && rc != ACMMP_ERR_ARG) return rc;
+                if (!pixels) return ACMMP_OK;
                 std::vector<float> &h = host[k - need.size()];
                 h.resize((size_t)cam.width * cam.height);
-                rc = acmmp_load_view(o_.dense.c_str(), id, size, h.data(), h.size(), &cam);
-                if (rc != ACMMP_OK) errs[k] = std::string("acmmp_load_view: ") + acmmp_pipeline_last_error();
-            }
-        };
-        std::vector<std::thread> pool;
-        const int nt = (int)std::min<size_t>((size_t)acmmp_host_threads(), nwork);
-        for (int t = 0; t < nt; ++t) pool.emplace_back(worker);
-        for (auto &t : pool) t.join();
-        for (size_t k = 0; k < nwork; ++k)
-            if (!errs[k].empty())
-                fail("view " + std::to_string(k < need.size() ? need[k] : problems_[(size_t)owned_[k - need.size()]].ref_image_id) +
-                     ": " + errs[k]);
+                return acmmp_load_view(o_.dense.c_str(), id, size, h.data(), h.size(), &cam);
+            },
+            [&](int i) {
+                return "view " + std::to_string(image_id((size_t)i)) + ": acmmp_load_view: " + acmmp_pipeline_last_error();
+            },
+            err);
+        if (load_rc) fail(err);
         // my refs: kept contiguous for JBU, and padded into my all-gather slots
         DevBuf send((size_t)slots_ * hmax_ * wmax_);
         hip_check(hipMemset(send.p, 0, send.n * sizeof(float)), "hipMemset");
@@ -592,20 +567,14 @@ class Driver {
         }
     }
 
-    // (h, w) of every view at this scale (acmmp_load_view's rescale rule)
+    // (h, w) of every view at this scale
     void shapes() {
         shape_.assign(problems_.size(), {0, 0});
         int hmax = 0, wmax = 0;
         for (size_t i = 0; i < problems_.size(); ++i) {
             int w = 0, h = 0;
-            acmmp_check(acmmp_image_size(image_path(o_.dense, problems_[i].ref_image_id).c_str(), &w, &h),
+            acmmp_check(acmmp_view_size(o_.dense.c_str(), problems_[i].ref_image_id, problems_[i].cur_image_size, &w, &h),
                         "image header");
-            const int m = problems_[i].cur_image_size;
-            if (w > m || h > m) {
-                const float f = std::min((float)m / (float)w, (float)m / (float)h);
-                w = (int)std::nearbyint((float)w * f);
-                h = (int)std::nearbyint((float)h * f);
-            }
             shape_[i] = {h, w};
             hmax = std::max(hmax, h);
             wmax = std::max(wmax, w);
@@ -860,19 +829,10 @@ class Driver {
         const std::string folder = result_folder(output_folder_, problems_[(size_t)v].ref_image_id);
         ::mkdir(folder.c_str(), 0777);
         const size_t P = (size_t)s.W * s.H;
-        std::vector<float> pl(P * 4), co(P), d(P), n(P * 3);
+        std::vector<float> pl(P * 4), co(P);
         hip_check(hipMemcpy(pl.data(), s.planes.p, pl.size() * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy");
         hip_check(hipMemcpy(co.data(), s.costs.p, co.size() * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy");
-        for (size_t k = 0; k < P; ++k) {
-            d[k] = pl[4 * k + 3];
-            n[3 * k + 0] = pl[4 * k + 0];
-            n[3 * k + 1] = pl[4 * k + 1];
-            n[3 * k + 2] = pl[4 * k + 2];
-        }
-        const std::string dn = folder + (geom ? "/depths_geom.dmb" : "/depths.dmb");
-        if (acmmp_write_dmb(dn.c_str(), s.H, s.W, 1, d.data()) ||
-            acmmp_write_dmb((folder + "/normals.dmb").c_str(), s.H, s.W, 3, n.data()) ||
-            acmmp_write_dmb((folder + "/costs.dmb").c_str(), s.H, s.W, 1, co.data()))
+        if (write_view_maps(folder, geom, s.H, s.W, pl.data(), co.data()))
             fail("cannot write the .dmb outputs of view " + std::to_string(problems_[(size_t)v].ref_image_id));
     }
 

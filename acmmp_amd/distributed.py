@@ -276,7 +276,7 @@ class ViewParallelPipeline:
         self.max_num_downscale = pipeline.compute_multiscale_settings(dense_folder, self.problems)
         costs = []
         for p in self.problems:
-            w, h = aio.image_size(self._image_path(p.ref_image_id))
+            w, h = aio.view_size(dense_folder, p.ref_image_id)
             costs.append(float(w * h * max(p.num_src_images, 1)))
         # the tail views are split in row bands over all ranks (engine runs
         # only: the injected CPU stand-ins compute whole views)
@@ -291,13 +291,6 @@ class ViewParallelPipeline:
         self.pass_log = []  # per pass: kind and wall seconds of its phases (tools/scale_sim.py)
 
     # ------------------------------------------------------------- inputs
-    def _image_path(self, image_id: int) -> str:
-        base = os.path.join(self.dense, "images", "%08d" % image_id)
-        for ext in (".jpg", ".pgm", ".pfm"):
-            if os.path.exists(base + ext):
-                return base + ext
-        return base + ".jpg"
-
     def _load_views(self):
         """Images + cameras of every image my views need, at their problem's
         cur_image_size (InputInitialization, src/ACMMP.cpp:536-598), decoded
@@ -382,15 +375,9 @@ class ViewParallelPipeline:
             torch.cuda.current_stream(self.tdev).synchronize()
 
     def _shapes(self):
-        shapes = {}
-        for i, p in enumerate(self.problems):
-            w, h = aio.image_size(self._image_path(p.ref_image_id))
-            m = p.cur_image_size
-            if w > m or h > m:
-                f = min(np.float32(m) / np.float32(w), np.float32(m) / np.float32(h))
-                w, h = int(np.round(np.float32(w) * f)), int(np.round(np.float32(h) * f))
-            shapes[i] = (h, w)
-        return shapes
+        """(h, w) of every view at its problem's cur_image_size."""
+        return {i: aio.view_size(self.dense, p.ref_image_id, p.cur_image_size)[::-1]
+                for i, p in enumerate(self.problems)}
 
     # --------------------------------------------------------------- pass
     def _map(self, tasks):

@@ -154,6 +154,19 @@ def image_size(path: str) -> tuple[int, int]:
     return w.value, h.value
 
 
+def view_size(dense_folder: str, image_id: int, max_image_size: int = 0) -> tuple[int, int]:
+    """(width, height) of a view at max_image_size, from its image's header:
+    InputInitialization's rescale rule (src/ACMMP.cpp:578-583), the size
+    acmmp_load_view gives it. max_image_size <= 0: the file's own size."""
+    import ctypes as C
+    lib = _abi.load_library()
+    w, h = C.c_int(0), C.c_int(0)
+    rc = lib.acmmp_view_size(dense_folder.encode(), image_id, max_image_size, C.byref(w), C.byref(h))
+    if rc != 0:
+        raise IOError(f"view {image_id}: {lib.acmmp_pipeline_last_error().decode(errors='replace')} (status {rc})")
+    return w.value, h.value
+
+
 def resize_linear(img: np.ndarray, width: int, height: int) -> np.ndarray:
     """cv::resize(..., INTER_LINEAR) of a float image (src/ACMMP.cpp:589)."""
     import ctypes as C

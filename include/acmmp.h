@@ -432,6 +432,11 @@ int acmmp_input_initialization(acmmp_ctx *ctx, const char *dense_folder, const c
  * when capacity suffices (else ACMMP_ERR_ARG). */
 int acmmp_load_view(const char *dense_folder, int image_id, int max_image_size, float *out, size_t capacity,
                     acmmp_camera *cam);
+/* The size acmmp_load_view gives view `image_id` at max_image_size, from the
+ * image's header alone: InputInitialization's rescale rule
+ * (src/ACMMP.cpp:578-583: float factor, std::round, unchanged when both sides
+ * are <= max_image_size). max_image_size <= 0: the file's own size. */
+int acmmp_view_size(const char *dense_folder, int image_id, int max_image_size, int *width, int *height);
 /* ~ ACMMP::CudaSpaceInitialization (src/ACMMP.cpp:638-809): previous-pass
  * plane/cost state of the reference view (geometric passes) and the
  * hierarchy inputs (low-res normals/costs + upsampled depth). */

@@ -76,7 +76,9 @@ def rescale(img, cam, max_image_size):
         return img, cam
     f32 = np.float32
     factor = min(f32(max_image_size) / f32(W), f32(max_image_size) / f32(H))
-    nw, nh = int(np.round(f32(W) * factor)), int(np.round(f32(H) * factor))
+    # std::round (src/ACMMP.cpp:578-583): halves away from zero = floor(x + 0.5)
+    # in float32 for these positive sizes
+    nw, nh = (int(np.floor(f32(d) * factor + f32(0.5))) for d in (W, H))
     sx, sy = f32(nw) / f32(W), f32(nh) / f32(H)
     K = list(cam.K)
     K[0], K[2], K[4], K[5] = f32(K[0]) * sx, f32(K[2]) * sx, f32(K[4]) * sy, f32(K[5]) * sy

@@ -146,7 +146,7 @@ def _dense(tmp_path, W, H, views=4):
     return d
 
 
-@pytest.mark.parametrize("W,H", [(96, 72), (1010, 760)])
+@pytest.mark.parametrize("W,H", [(96, 72), (1010, 760), (1004, 753)])  # the last: 376.5 rows at the first scale
 def test_world2_equals_world1(tmp_path, W, H):
     dense = _dense(tmp_path, W, H)
     mine1 = _run_world(dense, "/W1", 1)

@@ -106,6 +106,31 @@ def test_world2_tcp_multi_scale_split_tail_matches_oracle_jacobi(ms3_dense, ms3_
     assert _compare(d + "/CVPMS3", ms3_oracle_maps) == 3 * 4
 
 
+@pytest.fixture(scope="module")
+def half_dense(tmp_path_factory):
+    """3 views at 1002x501: the smallest size with a second scale (longer side
+    > 1000) whose first scale hits a half, 501 x 250.5 -> 251 rows by the
+    reference's std::round (src/ACMMP.cpp:578-583), 250 by round-half-even."""
+    d = str(tmp_path_factory.mktemp("dense_half"))
+    sc = scene.make_scene(num_views=3, width=1002, height=501)
+    scene.write_dense_folder(sc, d, num_src=2)
+    return d
+
+
+@pytest.fixture(scope="module")
+def half_oracle_maps(half_dense):
+    return OraclePipeline(half_dense).run_multi_scale("jacobi")
+
+
+@pytest.mark.timeout(900)
+def test_world2_tcp_multi_scale_half_size_matches_oracle_jacobi(half_dense, half_oracle_maps):
+    """The driver's shapes follow the loaded views where the rescale rounds a
+    half (the padded all-gathers and the row bands of the third view, at the
+    odd height 251, are sized from them), every .dmb bit-exact."""
+    _launch(half_dense, "/CVPH", 2, "tcp", ["--no_fusion"], timeout=600)
+    assert _compare(half_dense + "/CVPH", half_oracle_maps) == 3 * 4
+
+
 @pytest.mark.timeout(900)
 def test_world2_tcp_cfg4_source_count(tmp_path):
     """cfg4's problem shape (each view with its 20 best sources, N = 21:
