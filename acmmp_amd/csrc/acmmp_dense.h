@@ -59,6 +59,12 @@ inline void scaled_size(int w, int h, int max_image_size, int *nw, int *nh) {
     if (w > max_image_size || h > max_image_size) rescaled_size(w, h, max_image_size, nw, nh);
 }
 
+// the camera of an image resized by (sx, sy): K rows 0 and 1 (src/ACMMP.cpp:193-196, :590-593)
+inline void scale_intrinsics(acmmp_camera &cam, float sx, float sy) {
+    cam.K[0] *= sx, cam.K[2] *= sx;
+    cam.K[4] *= sy, cam.K[5] *= sy;
+}
+
 // cur_image_size of every problem for the next scale (src/main_ACMMP.cpp:99-106)
 inline void scale_step(acmmp_problem *problems, int n) {
     for (int i = 0; i < n; ++i)

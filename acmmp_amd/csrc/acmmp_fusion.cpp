@@ -1,24 +1,39 @@
-// acmmp_fusion.cpp — RunFusion (src/acmmp_definitions.cpp:828-1043), SURVEY
-// §8f rank 3: depth/normal maps of all views -> one coloured point cloud
-// (<out>/ACMMP_model.ply, StoreColorPlyFileBinaryPointCloud src/ACMMP.cpp:
-// 382-424).
+// acmmp_fusion.cpp — RunFusion (src/acmmp_definitions.cpp:828-1043), SURVEY §8f rank 3:
+// depth/normal maps of all views -> one coloured point cloud (<out>/ACMMP_model.ply,
+// StoreColorPlyFileBinaryPointCloud src/ACMMP.cpp:382-424), and RunPriorAwareFusion (:573-826,
+// <out>/ACMMP_prior_model.ply).
 //
-// Host code, literal: the reference's fusion is order-dependent (a pixel's
-// approval masks pixels of other views that later pixels then skip, and
-// used_list is never reset between pixels), so approvals run sequentially in
-// the reference's order with the reference's float expression order; the
-// per-pixel projections and tests before them run on host threads per band
-// of rows and are re-checked against the masks at approval time (exact: masks
-// only ever go 0 -> 1)
-// (Get3DPointonWorld / ProjectonCamera src/ACMMP.cpp:203-251, GetAngle
-// :253-262). Deviations: no cv::imshow (:897-900); the PLY is written in
-// point order (the reference's OpenMP-critical writes make its order
-// arbitrary); a colour image whose size differs from its depth map is resized
-// with a float bilinear filter (cv::resize's 8-bit fixed-point path is
+// Host code, literal: the reference's fusion is order-dependent (a pixel's approval masks pixels of
+// other views that later pixels then skip, and used_list is never reset between pixels), so
+// approvals run sequentially in the reference's order with the reference's float expression order
+// (Get3DPointonWorld / ProjectonCamera src/ACMMP.cpp:203-251, GetAngle :253-262). Only the
+// per-pixel projections and tests before an approval run on other threads. That is exact because
+// masks only ever go 0 -> 1 and depths do not change: a source or pixel found masked stays masked,
+// so the candidate stage may read the masks as they stand at any moment, and the walk re-checks
+// what passed against the masks as they stand at approval.
+//
+// The file, in order (RunFusion unless said otherwise):
+//   world_point .. stage_reproject   the reference's float expressions
+//   CacheDomain, Pool, pool_for      one L3 domain: the caller walks, workers do the rest
+//   MaskBits, Scene                  a fusion's inputs; masks one bit a pixel
+//   load_view .. resolve_sources     one view loader and source lookup for both fusions
+//   store_ply                        27-byte records in chunks (pool or caller)
+//   candidates_row  (pool workers, a row each; InFlight holds the job and waits
+//                   on every way out) a view's live pixels and their hits:
+//                   (source slot, source pixel, exp(-index)), source-major
+//   walk_view       (calling thread, the masks' only writer) the reference's
+//                   pixel order over those hits: points out, mask bits set;
+//                   view i + 1's candidates run beside it into the other ViewHits
+//   metric_of .. candidates          the prior-aware fusion's per-pixel tests
+//   acmmp_run_fusion                 load, resolve, wait i / start i + 1 / walk i, PLY
+//   acmmp_run_prior_aware_fusion     the same two steps per band of 32 rows, byte masks
+//
+// Deviations: no cv::imshow (:897-900); the PLY is written in point order (the reference's
+// OpenMP-critical writes make its order arbitrary); a colour image whose size differs from its
+// depth map is resized with a float bilinear filter (cv::resize's 8-bit fixed-point path is
 // unpinned).
 #include <sched.h>
 #include <fcntl.h>
-#include <sys/stat.h>
 #include <unistd.h>
 
 #include <algorithm>
@@ -102,7 +117,7 @@ float get_angle(const float *a, const float *b) {  // GetAngle
     return angle;
 }
 
-// RunFusion phase 1's two arithmetic stages (see phase1 below): branch-free
+// The two arithmetic stages of RunFusion's candidates_row: branch-free
 // loops the vectoriser turns into AVX2 where the host has it. Each is built
 // twice (target_clones: an AVX2 clone and a baseline x86-64 clone, picked by
 // the loader from the running CPU), so the library never executes an AVX2
@@ -287,12 +302,15 @@ class Pool {
 // RunFusion's per-view masks as bitsets: a view's ~20 sources' masks then
 // stay cache-resident during the approval walk (1 bit instead of 1 byte a
 // pixel). The walk is their only writer; the next view's candidate phase
-// reads them meanwhile (any value read is exact, see RunFusion): relaxed
+// reads them meanwhile (any value read is exact, see the top): relaxed
 // atomic words.
 struct MaskBits {
     std::vector<uint64_t> w;
     void assign(size_t n) { w.assign((n + 63) / 64, 0ull); }
-    bool get(size_t k) const { return (__atomic_load_n(&w[k >> 6], __ATOMIC_RELAXED) >> (k & 63)) & 1ull; }
+    static bool bit(const uint64_t *w, size_t k) {
+        return (__atomic_load_n(&w[k >> 6], __ATOMIC_RELAXED) >> (k & 63)) & 1ull;
+    }
+    bool get(size_t k) const { return bit(w.data(), k); }
     void set(size_t k) {  // single writer
         const uint64_t v = __atomic_load_n(&w[k >> 6], __ATOMIC_RELAXED) | (1ull << (k & 63));
         __atomic_store_n(&w[k >> 6], v, __ATOMIC_RELAXED);
@@ -315,19 +333,6 @@ int pool_for(Pool &pool, int n, Fn fn) {
             f_err = msg[(size_t)i];
             return rc[(size_t)i];
         }
-    return ACMMP_OK;
-}
-
-int read_dmb(const std::string &path, std::vector<float> &d, int &h, int &w, int &nb) {
-    int32_t hh = 0, ww = 0, bb = 0;
-    int rc = acmmp_read_dmb(path.c_str(), &hh, &ww, &bb, nullptr, 0);
-    if (rc != ACMMP_OK && rc != ACMMP_ERR_ARG) return ffail(ACMMP_ERR_IO, "cannot read %s", path.c_str());
-    d.resize((size_t)hh * ww * bb);
-    if (acmmp_read_dmb(path.c_str(), &hh, &ww, &bb, d.data(), d.size()))
-        return ffail(ACMMP_ERR_IO, "cannot read %s", path.c_str());
-    h = hh;
-    w = ww;
-    nb = bb;
     return ACMMP_OK;
 }
 
@@ -358,6 +363,111 @@ void resize_u8(const std::vector<uint8_t> &src, int sw, int sh, int C, std::vect
             }
         }
     }
+}
+
+// A fusion's inputs, per view. The stages read it; walk_view alone writes (mask bits only).
+struct Scene {
+    const acmmp_problem *problems;
+    std::vector<std::vector<uint8_t>> images;  // BGR, at the maps' size
+    std::vector<acmmp_camera> cameras;         // ... and so are their intrinsics
+    std::vector<std::vector<float>> depths, normals;
+    std::vector<int> rows, cols;
+    std::vector<MaskBits> masks;              // RunFusion's (the prior-aware fusion keeps bytes)
+    std::vector<std::vector<int>> src_index;  // [view][source slot j]: the source's view index
+    Scene(const acmmp_problem *p, size_t n)
+        : problems(p), images(n), cameras(n), depths(n), normals(n), rows(n), cols(n), masks(n), src_index(n) {}
+    size_t pixels() const {  // of all views: a cloud has at most one point per pixel
+        size_t total = 0;
+        for (size_t i = 0; i < rows.size(); ++i) total += (size_t)cols[i] * rows[i];
+        return total;
+    }
+};
+
+// depths[_geom].dmb and normals.dmb of view `id` in `folder`: one size, 1 and 3 bands
+int read_maps(const std::string &folder, const char *suffix, int id, std::vector<float> &depth,
+              std::vector<float> &normal, int &h, int &w) {
+    int nb = 0, h2 = 0, w2 = 0, nb2 = 0;
+    const std::string dpath = folder + suffix, npath = folder + "/normals.dmb";
+    if (acmmp_hostio::read_dmb(dpath, depth, h, w, nb)) return ffail(ACMMP_ERR_IO, "cannot read %s", dpath.c_str());
+    if (acmmp_hostio::read_dmb(npath, normal, h2, w2, nb2)) return ffail(ACMMP_ERR_IO, "cannot read %s", npath.c_str());
+    if (nb != 1 || nb2 != 3 || h2 != h || w2 != w) return ffail(ACMMP_ERR_IO, "bad maps for view %d", id);
+    return ACMMP_OK;
+}
+
+// View i of a fusion (both fusions; one index per thread): its colour image,
+// camera and the maps in `maps_folder`, image and intrinsics brought to the
+// maps' size (RescaleImageAndCamera, src/ACMMP.cpp:181-201).
+int load_view(Scene &sc, size_t i, const std::string &image_folder, const std::string &dense,
+              const std::string &maps_folder, const char *suffix) {
+    const int id = sc.problems[i].ref_image_id;
+    const std::string ipath = image_folder + "/" + id8(id) + ".jpg";
+    int iw = 0, ih = 0, h = 0, w = 0;
+    std::vector<uint8_t> img;
+    int rc = acmmp_internal_read_image_bgr(ipath.c_str(), img, iw, ih);
+    if (rc) return ffail(rc, "cannot read image %s", ipath.c_str());
+    const std::string cpath = camera_path(dense, id);
+    acmmp_camera &cam = sc.cameras[i];
+    if (acmmp_read_camera(cpath.c_str(), &cam)) return ffail(ACMMP_ERR_IO, "cannot read %s", cpath.c_str());
+    rc = read_maps(maps_folder, suffix, id, sc.depths[i], sc.normals[i], h, w);
+    if (rc) return rc;
+    sc.rows[i] = h;
+    sc.cols[i] = w;
+    if (w == iw && h == ih) {
+        sc.images[i] = std::move(img);
+    } else {
+        resize_u8(img, iw, ih, 3, sc.images[i], w, h);
+        acmmp_dense::scale_intrinsics(cam, w / static_cast<float>(iw), h / static_cast<float>(ih));
+        cam.width = w;
+        cam.height = h;
+    }
+    return ACMMP_OK;
+}
+
+// RunFusion's mask folder (:881-905): mask = (resize(mask) < 128) / 255 as bits of `mask` (w x h, all 0)
+int load_initial_mask(const std::string &mpath, int w, int h, MaskBits &mask) {
+    int mw = 0, mh = 0, mc = 0, bd = 0;
+    std::vector<uint16_t> m16;
+    if (acmmp_hostio::read_png(mpath, m16, mw, mh, mc, bd))
+        return ffail(ACMMP_ERR_IO, "Couldn't find mask image %s", mpath.c_str());
+    // cv::imread(path, -1) keeps the file's depth and channels (colour as
+    // B, G, R[, A], as acmmp_read_png returns them too); `(temp_mask < 128) /
+    // 255` keeps the channels, and the walk reads and writes the mask with
+    // at<uchar>(r, c): byte c of row r. For a 1-channel mask that is pixel
+    // (r, c); for a colour one it is channel c % C of pixel c / C, reproduced
+    // here. (2-channel gray+alpha masks use the gray value: unpinned.)
+    const bool same = mw == w && mh == h;
+    if (bd != 8 && !same) return ffail(ACMMP_ERR_UNSUPPORTED, "16-bit mask %s needs resizing", mpath.c_str());
+    const int C = mc == 2 ? 1 : mc;
+    std::vector<uint16_t> px((size_t)mw * mh * C);
+    for (size_t k = 0; k < (size_t)mw * mh; ++k)
+        for (int ch = 0; ch < C; ++ch) px[k * C + ch] = m16[k * mc + ch];
+    std::vector<uint16_t> mr;
+    if (same) {
+        mr.swap(px);
+    } else {
+        std::vector<uint8_t> m8(px.begin(), px.end()), r8;
+        resize_u8(m8, mw, mh, C, r8, w, h);
+        mr.assign(r8.begin(), r8.end());
+    }
+    for (int r = 0; r < h; ++r)
+        for (int c = 0; c < w; ++c)
+            if (mr[(size_t)r * w * C + c] < 128) mask.set((size_t)r * w + c);
+    return ACMMP_OK;
+}
+
+// src_index from the problems' image ids: every source must be a problem itself
+int resolve_sources(Scene &sc) {
+    std::map<int, int> image_id_2_index;
+    for (size_t i = 0; i < sc.rows.size(); ++i) image_id_2_index[sc.problems[i].ref_image_id] = (int)i;
+    for (size_t i = 0; i < sc.rows.size(); ++i)
+        for (int j = 0; j < sc.problems[i].num_src_images; ++j) {
+            const auto it = image_id_2_index.find(sc.problems[i].src_image_ids[j]);
+            if (it == image_id_2_index.end())
+                return ffail(ACMMP_ERR_ARG, "source %d of view %d is not a problem", sc.problems[i].src_image_ids[j],
+                             sc.problems[i].ref_image_id);
+            sc.src_index[i].push_back(it->second);
+        }
+    return ACMMP_OK;
 }
 
 struct Point {
@@ -426,6 +536,262 @@ int store_ply(const std::string &path, const std::vector<Point> &pc, Pool *pool 
     return rc;
 }
 
+// ---- RunFusion's two stages per view (see the top for why they are exact).
+// A hit = (source slot j, source pixel sp) packed in 32 bits; its
+// exp(-tmp_index) is kept beside it, and every live pixel's sum of them
+// (ascending j, as the walk adds) is precomputed: the walk reads the
+// per-hit values only for pixels where some hit became masked.
+constexpr int kSpBits = 27;
+constexpr uint32_t kSpMask = (1u << kSpBits) - 1;
+constexpr uint32_t kNoHit = 0xffffffffu;
+
+struct ViewHits {
+    std::vector<std::vector<uint32_t>> hit;    // hits of row r, pixel order: j << kSpBits | sp
+    std::vector<std::vector<float>> ex;        // their exp(-tmp_index)
+    // per live pixel of row r (the candidate stage's order: ascending column)
+    // -- the walk visits only these (a pixel not live then stays so:
+    // masks only go 0 -> 1 and depths do not change)
+    std::vector<std::vector<int>> live;        // its column
+    std::vector<std::vector<uint16_t>> nhit;   // its number of hits
+    std::vector<std::vector<float>> sum;       // sum of its hits' ex, ascending j
+    std::vector<std::vector<F3>> X;            // its world point
+    void resize(size_t rows) {
+        hit.resize(rows), ex.resize(rows), live.resize(rows), nhit.resize(rows), sum.resize(rows), X.resize(rows);
+    }
+};
+
+struct RowScratch {
+    std::vector<F3> X;
+    std::vector<int> live;           // columns of the live pixels
+    std::vector<uint32_t> sp;        // [live k][j]: source pixel of a hit, or kNoHit
+    std::vector<float> e;            // [live k][j]: its exp(-tmp_index)
+    // one source's pass over the row, in stages (see candidates_row)
+    std::vector<int> src_c, src_r;   // [live k]: the projected source pixel
+    std::vector<int> cand;           // live indices whose source pixel is in bounds, unmasked, depth > 0
+    std::vector<int> ccol, csc, csr; // ... its column and source pixel
+    std::vector<float> cdepth, cref; // ... its source depth and reference depth
+    std::vector<float> rerr, rdiff;  // [cand q]: reprojection error, relative depth difference
+};
+
+// Row r of view i: every pixel's per-source projections and consistency tests against the masks as
+// they stand. Source-major inside the row: every live pixel's world point first, then one source at
+// a time over the row (its depth/normal/mask reads follow the row's projection into that source
+// instead of hopping between 20 sources per pixel), then each pixel's hits in ascending j as the
+// reference adds them (same values, same order).
+void candidates_row(const Scene &sc, size_t i, int r, ViewHits &vh) {
+    thread_local RowScratch rs;
+    const int W = sc.cols[i];
+    const int num_ngb = sc.problems[i].num_src_images;
+    const float depth_max = sc.cameras[i].depth_max;
+    std::vector<uint32_t> &h = vh.hit[(size_t)r];
+    std::vector<float> &hx = vh.ex[(size_t)r];
+    std::vector<uint16_t> &nh = vh.nhit[(size_t)r];
+    std::vector<float> &sum = vh.sum[(size_t)r];
+    std::vector<F3> &X = vh.X[(size_t)r];
+    h.clear();
+    hx.clear();
+    rs.live.clear();
+    rs.X.clear();
+    for (int c = 0; c < W; ++c) {
+        const size_t pc = (size_t)r * W + c;
+        if (sc.masks[i].get(pc)) continue;
+        const float ref_depth = sc.depths[i][pc];
+        if (ref_depth <= 0.0 || ref_depth >= depth_max) continue;
+        rs.live.push_back(c);
+        rs.X.push_back(world_point(c, r, ref_depth, sc.cameras[i]));
+    }
+    const size_t nl = rs.live.size();
+    const size_t nj = (size_t)std::max(num_ngb, 1);
+    rs.sp.assign(nl * nj, kNoHit);
+    rs.e.resize(nl * nj);
+    nh.resize(nl);
+    sum.resize(nl);
+    rs.src_c.resize(nl);
+    rs.src_r.resize(nl);
+    for (int j = 0; j < num_ngb; ++j) {
+        const int s = sc.src_index[i][j];
+        const int src_cols = sc.cols[s], src_rows = sc.rows[s];
+        // Per source, the reference's per-pixel test in four stages over
+        // the row's live pixels (the same operations on the same values:
+        // the two arithmetic stages are branch-free loops the compiler
+        // vectorises; the gathers and the mask reads stay scalar).
+        // (1) the projection into the source
+        stage_project(rs.X.data(), nl, sc.cameras[s], rs.src_c.data(), rs.src_r.data());
+        // (2) in bounds, unmasked, positive source depth: the candidates,
+        // with what stage 3 reads, in contiguous arrays
+        rs.cand.resize(nl);
+        rs.ccol.resize(nl);
+        rs.csc.resize(nl);
+        rs.csr.resize(nl);
+        rs.cdepth.resize(nl);
+        rs.cref.resize(nl);
+        size_t nc = 0;
+        const float *dref = sc.depths[i].data() + (size_t)r * W;
+        for (size_t k = 0; k < nl; ++k) {
+            const int src_r = rs.src_r[k], src_c = rs.src_c[k];
+            if (!(src_c >= 0 && src_c < src_cols && src_r >= 0 && src_r < src_rows)) continue;
+            const size_t sp = (size_t)src_r * src_cols + src_c;
+            if (sc.masks[s].get(sp)) continue;
+            const float src_depth = sc.depths[s][sp];
+            if (src_depth <= 0.0) continue;
+            rs.cand[nc] = (int)k;
+            rs.ccol[nc] = rs.live[k];
+            rs.csc[nc] = src_c;
+            rs.csr[nc] = src_r;
+            rs.cdepth[nc] = src_depth;
+            rs.cref[nc] = dref[rs.live[k]];
+            ++nc;
+        }
+        // (3) the reprojection into view i: error and relative depth difference
+        rs.rerr.resize(nc);
+        rs.rdiff.resize(nc);
+        stage_reproject(nc, r, rs.ccol.data(), rs.csc.data(), rs.csr.data(), rs.cdepth.data(), rs.cref.data(),
+                        rs.rerr.data(), rs.rdiff.data(), sc.cameras[s], sc.cameras[i]);
+        // (4) the reference evaluates all three before the test; acos is
+        // pure, so the angle is only formed where the first two pass
+        for (size_t q = 0; q < nc; ++q) {
+            const float reproj_error = rs.rerr[q], relative_depth_diff = rs.rdiff[q];
+            if (!(reproj_error < 2.0f && relative_depth_diff < 0.01f)) continue;
+            const int k = rs.cand[q];
+            const size_t pc = (size_t)r * W + rs.ccol[q];
+            const size_t sp = (size_t)rs.csr[q] * src_cols + rs.csc[q];
+            const float angle = get_angle(&sc.normals[i][pc * 3], &sc.normals[s][sp * 3]);
+            if (angle < 0.174533f) {
+                const float tmp_index = reproj_error + 200 * relative_depth_diff + angle * 10;
+                rs.sp[(size_t)k * nj + (size_t)j] = (uint32_t)sp;
+                rs.e[(size_t)k * nj + (size_t)j] = std::exp(-tmp_index);
+            }
+        }
+    }
+    for (size_t k = 0; k < nl; ++k) {
+        const size_t k0 = h.size();
+        float total = 0;
+        for (int j = 0; j < num_ngb; ++j) {
+            const uint32_t sp = rs.sp[k * nj + (size_t)j];
+            if (sp == kNoHit) continue;
+            const float e = rs.e[k * nj + (size_t)j];
+            h.push_back((uint32_t)j << kSpBits | sp);
+            hx.push_back(e);
+            total += e;
+        }
+        nh[k] = (uint16_t)(h.size() - k0);
+        sum[k] = total;
+    }
+    // the walk emits an approved pixel's point from here (the same
+    // world_point call the reference makes at approval, :1012)
+    X.swap(rs.X);
+    vh.live[(size_t)r].swap(rs.live);
+}
+
+// A view's candidate job on the pool. Its rows read the scene and write a
+// ViewHits buffer, so it must be over before either dies: declare this after
+// both, and every way out of the scope waits first.
+struct InFlight {
+    Pool &pool;
+    std::shared_ptr<Pool::Job> job;
+    ~InFlight() { wait(); }
+    void start(const Scene &sc, size_t i, ViewHits &vh) {
+        vh.resize((size_t)sc.rows[i]);
+        job = pool.submit(sc.rows[i], [&sc, &vh, i](int r) { candidates_row(sc, i, r, vh); });
+    }
+    void wait() {
+        if (job) pool.wait(job);
+        job.reset();
+    }
+};
+
+struct WalkStats {
+    size_t n_live = 0, n_hits = 0, n_masked = 0;
+    double t_wait = 0, t_walk = 0;
+};
+
+// The approval walk of view i, in the reference's pixel order: the sources that passed in the
+// candidate stage are re-checked against the current masks and accumulated in ascending j (same exp
+// values, same sum order), then points are emitted and masks / used_list updated. `approved`, if
+// not null, is the view's W x H debug image.
+void walk_view(Scene &sc, size_t i, const ViewHits &vh, int con_num_thresh, float consistency_scalar,
+               std::vector<Point> &cloud, uint8_t *approved, WalkStats &stats) {
+    const int W = sc.cols[i], H = sc.rows[i];
+    const int num_ngb = sc.problems[i].num_src_images;
+    size_t n_live = 0, n_hits = 0, n_masked = 0;
+    // per source: its mask words; used_list as mask indices (-1 unset)
+    std::vector<uint64_t *> mw((size_t)std::max(num_ngb, 1));
+    for (int j = 0; j < num_ngb; ++j) mw[(size_t)j] = sc.masks[(size_t)sc.src_index[i][j]].w.data();
+    std::vector<int64_t> used_sp((size_t)std::max(num_ngb, 1), -1);
+    uint32_t dirty = 0;  // used_sp entries written since the last approval
+    for (int r = 0; r < H; ++r) {
+        const uint32_t *h = vh.hit[(size_t)r].data();
+        const float *hx = vh.ex[(size_t)r].data();
+        const std::vector<int> &lv = vh.live[(size_t)r];
+        const uint16_t *nhr = vh.nhit[(size_t)r].data();
+        const float *sumr = vh.sum[(size_t)r].data();
+        const F3 *xr = vh.X[(size_t)r].data();
+        const size_t nl = lv.size();
+        for (size_t k = 0; k < nl; ++k) {  // the pixels live in the candidate stage, in column order
+            const int c = lv[k];
+            const size_t pc = (size_t)r * W + c;
+            const int nh = nhr[k];
+            const uint32_t *hp = h;
+            const float *hxp = hx;
+            const F3 *xp = xr + k;
+            h += nh;
+            hx += nh;
+            // re-read: view i - 1's walk (beside view i's candidate stage) and,
+            // if i is its own source, view i's own approvals set bits
+            if (sc.masks[i].get(pc)) continue;
+            int num_consistent = 0;
+            bool masked = false;
+            for (int q = 0; q < nh; ++q) {
+                const uint32_t j = hp[q] >> kSpBits, sp = hp[q] & kSpMask;
+                if (MaskBits::bit(mw[j], sp)) {
+                    masked = true;
+                    continue;
+                }
+                used_sp[j] = sp;
+                dirty |= 1u << j;
+                num_consistent++;
+            }
+            float dynamic_consistency = sumr[k];
+            n_live++;
+            n_hits += (size_t)nh;
+            n_masked += masked;
+            if (masked) {  // re-add the unmasked ones, ascending j
+                dynamic_consistency = 0;
+                for (int q = 0; q < nh; ++q)
+                    if (!MaskBits::bit(mw[hp[q] >> kSpBits], hp[q] & kSpMask)) dynamic_consistency += hxp[q];
+            }
+            if (num_consistent >= con_num_thresh && (dynamic_consistency > consistency_scalar * num_consistent)) {
+                const float *ref_normal = &sc.normals[i][pc * 3];
+                const uint8_t *bgr = &sc.images[i][pc * 3];
+                Point p;
+                p.coord = *xp;  // world_point(c, r, depths[i][pc], cameras[i]), formed in the candidate stage
+                p.normal = F3{ref_normal[0], ref_normal[1], ref_normal[2]};
+                p.color = F3{(float)bgr[0], (float)bgr[1], (float)bgr[2]};
+                cloud.push_back(p);
+                // used_list is not reset per pixel in the reference: stale
+                // entries apply too. An entry unchanged since the last
+                // approval was set then (masks only go 0 -> 1), so only
+                // the entries written since are applied.
+                for (; dirty; dirty &= dirty - 1) {
+                    const int j = __builtin_ctz(dirty);
+                    const int64_t sp = used_sp[(size_t)j];
+                    const int s = sc.src_index[i][j];
+                    sc.masks[s].set((size_t)sp);
+                    if (approved) {
+                        // `approved` is this view's W x H image indexed by source coordinates (:1030)
+                        const int ux = (int)(sp % sc.cols[s]), uy = (int)(sp / sc.cols[s]);
+                        if (uy < H && ux < W) approved[(size_t)uy * W + ux] = 255;
+                    }
+                }
+            }
+        }
+    }
+    stats.n_live += n_live, stats.n_hits += n_hits, stats.n_masked += n_masked;
+}
+
+using Clock = std::chrono::steady_clock;
+double secs(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double>(b - a).count(); }
+
 // ---- prior-aware fusion helpers (src/acmmp_definitions.cpp:443-571)
 struct CInfo {  // struct c_info
     float dynamic_consistency = 0;
@@ -438,10 +804,9 @@ struct CMetric {  // struct cmetric
     float reproj_err = 1e6, relative_depth_diff = 1e6, angle = 1e6;
 };
 
-struct FusionInputs {
-    std::vector<acmmp_camera> cameras;
-    std::vector<std::vector<float>> depths, normals, pdepths, pnormals;
-    std::vector<int> rows, cols;
+struct FusionInputs : Scene {  // with the second map pair: this run's priors
+    std::vector<std::vector<float>> pdepths, pnormals;
+    FusionInputs(const acmmp_problem *p, size_t n) : Scene(p, n), pdepths(n), pnormals(n) {}
 };
 
 CMetric metric_of(const FusionInputs &in, size_t i, int r, int c, float ref_depth, const float *ref_normal, int src,
@@ -509,7 +874,6 @@ void candidates(const FusionInputs &in, const std::vector<std::vector<uint8_t>> 
 
 }  // namespace
 
-
 extern "C" {
 
 const char *acmmp_fusion_last_error(void) { return f_err.c_str(); }
@@ -521,387 +885,67 @@ int acmmp_run_fusion(const char *dense_folder, const char *output_folder, const 
     const std::string dense = dense_folder, out = output_folder;
     const std::string image_folder = dense + (image_dir ? image_dir : "/images");
     const bool use_masks = mask_folder && std::string(mask_folder) != " " && mask_folder[0] != 0;
+    const char *suffix = geom_consistency ? "/depths_geom.dmb" : "/depths.dmb";
     const size_t n = (size_t)count;
-    std::vector<std::vector<uint8_t>> images(n);
-    std::vector<MaskBits> masks(n);
-    std::vector<acmmp_camera> cameras(n);
-    std::vector<std::vector<float>> depths(n), normals(n);
-    std::vector<int> rows(n), cols(n);
-    std::map<int, int> image_id_2_index;
-    for (size_t i = 0; i < n; ++i) image_id_2_index[problems[i].ref_image_id] = (int)i;
     const bool timing = std::getenv("ACMMP_HOST_TIMING") != nullptr;
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    auto secs = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
-        return std::chrono::duration<double>(b - a).count();
-    };
-    const auto t_start = now();
-    double t_wait = 0, t_walk = 0;
-    size_t n_live = 0, n_hits = 0, n_masked = 0;
-    // The threads are confined to one last-level-cache domain BEFORE the
-    // loads, and the loads run on that domain's pool: the maps, images and
-    // masks are then first touched (allocated) on the memory node of the
-    // walk's core, which reads them. (Loaded by threads spread over the whole
-    // machine, a 2-socket host put part of them on the other node, and the
-    // walk measured 0.85 or 1.3 s from run to run, profiles/r05_fusion_walk_ab3.jsonl.)
+    const auto t_start = Clock::now();
+    Scene sc(problems, n);
+    // The threads are confined to one last-level-cache domain BEFORE the loads, and the loads run on
+    // that domain's pool: maps, images and masks are then first touched (allocated) on the memory node
+    // of the walk's core, which reads them. (Loaded by threads all over a 2-socket host, part of them
+    // lay on the other node: walk 0.85 or 1.3 s from run to run, profiles/r05_fusion_walk_ab3.jsonl.)
     CacheDomain dom;
     Pool pool(&dom);
     // views load independently (JPEG decode, two .dmb reads, optional mask)
-    int load_rc = pool_for(pool, (int)n, [&](int vi) -> int {
+    int rc = pool_for(pool, (int)n, [&](int vi) -> int {
         const size_t i = (size_t)vi;
         const int id = problems[i].ref_image_id;
-        const std::string ipath = image_folder + "/" + id8(id) + ".jpg";
-        int iw = 0, ih = 0;
-        std::vector<uint8_t> img;
-        int rc = acmmp_internal_read_image_bgr(ipath.c_str(), img, iw, ih);
-        if (rc) return ffail(rc, "cannot read image %s", ipath.c_str());
-        const std::string cpath = camera_path(dense, id);
-        if (acmmp_read_camera(cpath.c_str(), &cameras[i])) return ffail(ACMMP_ERR_IO, "cannot read %s", cpath.c_str());
-        const std::string rf = result_folder(out, id);
-        int h, w, nb, h2, w2, nb2;
-        rc = read_dmb(rf + (geom_consistency ? "/depths_geom.dmb" : "/depths.dmb"), depths[i], h, w, nb);
-        if (!rc) rc = read_dmb(rf + "/normals.dmb", normals[i], h2, w2, nb2);
-        if (rc) return rc;
-        if (nb != 1 || nb2 != 3 || h2 != h || w2 != w) return ffail(ACMMP_ERR_IO, "bad maps for view %d", id);
-        rows[i] = h;
-        cols[i] = w;
-        // RescaleImageAndCamera (src/ACMMP.cpp:181-201)
-        if (w == iw && h == ih) {
-            images[i] = std::move(img);
-        } else {
-            const float scale_x = w / static_cast<float>(iw);
-            const float scale_y = h / static_cast<float>(ih);
-            resize_u8(img, iw, ih, 3, images[i], w, h);
-            cameras[i].K[0] *= scale_x;
-            cameras[i].K[2] *= scale_x;
-            cameras[i].K[4] *= scale_y;
-            cameras[i].K[5] *= scale_y;
-            cameras[i].width = w;
-            cameras[i].height = h;
-        }
-        masks[i].assign((size_t)w * h);
-        if (use_masks) {  // :881-905: mask = (resize(mask) < 128) / 255
-            const std::string mpath = dense + "/" + mask_folder + "/" + id8(id) + ".png";
-            int mw = 0, mh = 0, mc = 0, bd = 0;
-            std::vector<uint16_t> m16;
-            rc = acmmp_read_png(mpath.c_str(), nullptr, 0, &mw, &mh, &mc, &bd);
-            if (rc == ACMMP_ERR_ARG) {
-                m16.resize((size_t)mw * mh * mc);
-                rc = acmmp_read_png(mpath.c_str(), m16.data(), m16.size(), &mw, &mh, &mc, &bd);
-            }
-            if (rc) return ffail(ACMMP_ERR_IO, "Couldn't find mask image %s", mpath.c_str());
-            // cv::imread(path, -1) keeps the file's depth and channels (colour
-            // as B, G, R[, A], as acmmp_read_png returns them too);
-            // `(temp_mask < 128) / 255` keeps the channels,
-            // and the walk reads and writes the mask with at<uchar>(r, c):
-            // byte c of row r. For a 1-channel mask that is pixel (r, c); for
-            // a colour one it is channel c % C of pixel c / C, reproduced here.
-            // (2-channel gray+alpha masks use the gray value: unpinned.)
-            const bool same = mw == w && mh == h;
-            if (bd != 8 && !same)
-                return ffail(ACMMP_ERR_UNSUPPORTED, "16-bit mask %s needs resizing", mpath.c_str());
-            const int C = mc == 2 ? 1 : mc;
-            std::vector<uint16_t> px((size_t)mw * mh * C);
-            for (size_t k = 0; k < (size_t)mw * mh; ++k)
-                for (int ch = 0; ch < C; ++ch) px[k * C + ch] = m16[k * mc + ch];
-            std::vector<uint16_t> mr;
-            if (same) {
-                mr.swap(px);
-            } else {
-                std::vector<uint8_t> m8(px.begin(), px.end()), r8;
-                resize_u8(m8, mw, mh, C, r8, w, h);
-                mr.assign(r8.begin(), r8.end());
-            }
-            for (int r = 0; r < h; ++r)
-                for (int c = 0; c < w; ++c)
-                    if (mr[(size_t)r * w * C + c] < 128) masks[i].set((size_t)r * w + c);
-        }
-        return (int)ACMMP_OK;
+        const int load_rc = load_view(sc, i, image_folder, dense, result_folder(out, id), suffix);
+        if (load_rc) return load_rc;
+        sc.masks[i].assign((size_t)sc.cols[i] * sc.rows[i]);
+        if (!use_masks) return (int)ACMMP_OK;
+        return load_initial_mask(dense + "/" + mask_folder + "/" + id8(id) + ".png", sc.cols[i], sc.rows[i],
+                                 sc.masks[i]);
     });
-    if (load_rc) return load_rc;
-
-    std::vector<std::vector<int>> src_index(n);
+    if (!rc) rc = resolve_sources(sc);
+    if (rc) return rc;
     for (size_t i = 0; i < n; ++i)
-        for (int j = 0; j < problems[i].num_src_images; ++j) {
-            auto it = image_id_2_index.find(problems[i].src_image_ids[j]);
-            if (it == image_id_2_index.end())
-                return ffail(ACMMP_ERR_ARG, "source %d of view %d is not a problem", problems[i].src_image_ids[j],
-                             problems[i].ref_image_id);
-            src_index[i].push_back(it->second);
-        }
-    // Two phases per view, exact to the sequential loop: (1) on the pool,
-    // every pixel's per-source projections and consistency tests against
-    // the masks as they stand (masks only ever go 0 -> 1, so a source or
-    // pixel masked when read stays masked); (2) on this thread, in the
-    // reference's pixel order, the sources that passed are re-checked
-    // against the current masks and accumulated in ascending j (same exp
-    // values, same sum order), then points are emitted and masks / used_list
-    // updated. View i + 1's phase 1 runs while view i is walked.
-    // A hit = (source slot j, source pixel sp) packed in 32 bits; its
-    // exp(-tmp_index) is kept beside it, and every live pixel's sum of them
-    // (ascending j, as the walk adds) is precomputed: the walk reads the
-    // per-hit values only for pixels where some hit became masked.
-    constexpr int kSpBits = 27;
-    struct ViewHits {
-        std::vector<std::vector<uint32_t>> hit;    // hits of row r, pixel order: j << kSpBits | sp
-        std::vector<std::vector<float>> ex;        // their exp(-tmp_index)
-        // per live pixel of row r (phase 1's order: ascending column) --
-        // the walk visits only these (a pixel not live in phase 1 stays so:
-        // masks only go 0 -> 1 and depths do not change)
-        std::vector<std::vector<int>> live;        // its column
-        std::vector<std::vector<uint16_t>> nhit;   // its number of hits
-        std::vector<std::vector<float>> sum;       // sum of its hits' ex, ascending j
-        std::vector<std::vector<F3>> X;            // its world point
-    };
-    for (size_t i = 0; i < n; ++i)
-        if ((size_t)cols[i] * rows[i] > (size_t(1) << kSpBits) || problems[i].num_src_images > 32)
+        if ((size_t)sc.cols[i] * sc.rows[i] > (size_t(1) << kSpBits) || problems[i].num_src_images > 32)
             return ffail(ACMMP_ERR_ARG, "view %d: fusion supports images up to 2^27 pixels and 32 sources",
                          problems[i].ref_image_id);
-    // Source-major inside a row: every live pixel's world point first, then
-    // one source at a time over the row (its depth/normal/mask reads follow
-    // the row's projection into that source instead of hopping between 20
-    // sources per pixel), then each pixel's hits in ascending j as the
-    // reference adds them (same values, same order).
-    struct RowScratch {
-        std::vector<F3> X;
-        std::vector<int> live;           // columns of the live pixels
-        std::vector<uint32_t> sp;        // [live k][j]: source pixel of a hit, or kNoHit
-        std::vector<float> e;            // [live k][j]: its exp(-tmp_index)
-        // one source's pass over the row, in stages (see phase1)
-        std::vector<int> src_c, src_r;   // [live k]: the projected source pixel
-        std::vector<int> cand;           // live indices whose source pixel is in bounds, unmasked, depth > 0
-        std::vector<int> ccol, csc, csr; // ... its column and source pixel
-        std::vector<float> cdepth, cref; // ... its source depth and reference depth
-        std::vector<float> rerr, rdiff;  // [cand q]: reprojection error, relative depth difference
-    };
-    constexpr uint32_t kNoHit = 0xffffffffu;
-    auto phase1 = [&](size_t i, ViewHits &vh, int r) {
-        thread_local RowScratch rs;
-        const int W = cols[i];
-        const int num_ngb = problems[i].num_src_images;
-        const float depth_max = cameras[i].depth_max;
-        std::vector<uint32_t> &h = vh.hit[(size_t)r];
-        std::vector<float> &hx = vh.ex[(size_t)r];
-        std::vector<uint16_t> &nh = vh.nhit[(size_t)r];
-        std::vector<float> &sum = vh.sum[(size_t)r];
-        std::vector<F3> &X = vh.X[(size_t)r];
-        h.clear();
-        hx.clear();
-        rs.live.clear();
-        rs.X.clear();
-        for (int c = 0; c < W; ++c) {
-            const size_t pc = (size_t)r * W + c;
-            if (masks[i].get(pc)) continue;
-            const float ref_depth = depths[i][pc];
-            if (ref_depth <= 0.0 || ref_depth >= depth_max) continue;
-            rs.live.push_back(c);
-            rs.X.push_back(world_point(c, r, ref_depth, cameras[i]));
-        }
-        const size_t nl = rs.live.size();
-        const size_t nj = (size_t)std::max(num_ngb, 1);
-        rs.sp.assign(nl * nj, kNoHit);
-        rs.e.resize(nl * nj);
-        nh.resize(nl);
-        sum.resize(nl);
-        rs.src_c.resize(nl);
-        rs.src_r.resize(nl);
-        for (int j = 0; j < num_ngb; ++j) {
-            const int s = src_index[i][j];
-            const int src_cols = cols[s], src_rows = rows[s];
-            // Per source, the reference's per-pixel test in four stages over
-            // the row's live pixels (the same operations on the same values:
-            // the two arithmetic stages are branch-free loops the compiler
-            // vectorises; the gathers and the mask reads stay scalar).
-            // (1) the projection into the source
-            stage_project(rs.X.data(), nl, cameras[s], rs.src_c.data(), rs.src_r.data());
-            // (2) in bounds, unmasked, positive source depth: the candidates,
-            // with what stage 3 reads, in contiguous arrays
-            rs.cand.resize(nl);
-            rs.ccol.resize(nl);
-            rs.csc.resize(nl);
-            rs.csr.resize(nl);
-            rs.cdepth.resize(nl);
-            rs.cref.resize(nl);
-            size_t nc = 0;
-            const float *dref = depths[i].data() + (size_t)r * W;
-            for (size_t k = 0; k < nl; ++k) {
-                const int src_r = rs.src_r[k], src_c = rs.src_c[k];
-                if (!(src_c >= 0 && src_c < src_cols && src_r >= 0 && src_r < src_rows)) continue;
-                const size_t sp = (size_t)src_r * src_cols + src_c;
-                if (masks[s].get(sp)) continue;
-                const float src_depth = depths[s][sp];
-                if (src_depth <= 0.0) continue;
-                rs.cand[nc] = (int)k;
-                rs.ccol[nc] = rs.live[k];
-                rs.csc[nc] = src_c;
-                rs.csr[nc] = src_r;
-                rs.cdepth[nc] = src_depth;
-                rs.cref[nc] = dref[rs.live[k]];
-                ++nc;
-            }
-            // (3) the reprojection into view i: error and relative depth difference
-            rs.rerr.resize(nc);
-            rs.rdiff.resize(nc);
-            stage_reproject(nc, r, rs.ccol.data(), rs.csc.data(), rs.csr.data(), rs.cdepth.data(), rs.cref.data(),
-                            rs.rerr.data(), rs.rdiff.data(), cameras[s], cameras[i]);
-            // (4) the reference evaluates all three before the test; acos is
-            // pure, so the angle is only formed where the first two pass
-            for (size_t q = 0; q < nc; ++q) {
-                const float reproj_error = rs.rerr[q], relative_depth_diff = rs.rdiff[q];
-                if (!(reproj_error < 2.0f && relative_depth_diff < 0.01f)) continue;
-                const int k = rs.cand[q];
-                const size_t pc = (size_t)r * W + rs.ccol[q];
-                const size_t sp = (size_t)rs.csr[q] * src_cols + rs.csc[q];
-                const float angle = get_angle(&normals[i][pc * 3], &normals[s][sp * 3]);
-                if (angle < 0.174533f) {
-                    const float tmp_index = reproj_error + 200 * relative_depth_diff + angle * 10;
-                    rs.sp[(size_t)k * nj + (size_t)j] = (uint32_t)sp;
-                    rs.e[(size_t)k * nj + (size_t)j] = std::exp(-tmp_index);
-                }
-            }
-        }
-        for (size_t k = 0; k < nl; ++k) {
-            const size_t k0 = h.size();
-            float total = 0;
-            for (int j = 0; j < num_ngb; ++j) {
-                const uint32_t sp = rs.sp[k * nj + (size_t)j];
-                if (sp == kNoHit) continue;
-                const float e = rs.e[k * nj + (size_t)j];
-                h.push_back((uint32_t)j << kSpBits | sp);
-                hx.push_back(e);
-                total += e;
-            }
-            nh[k] = (uint16_t)(h.size() - k0);
-            sum[k] = total;
-        }
-        // the walk emits an approved pixel's point from here (the same
-        // world_point call the reference makes at approval, :1012)
-        X.swap(rs.X);
-        vh.live[(size_t)r].swap(rs.live);
-    };
-    std::vector<ViewHits> vhits(2);
-    auto start_phase1 = [&](size_t i) {
-        ViewHits &vh = vhits[i & 1];
-        vh.hit.resize((size_t)rows[i]);
-        vh.ex.resize((size_t)rows[i]);
-        vh.live.resize((size_t)rows[i]);
-        vh.nhit.resize((size_t)rows[i]);
-        vh.sum.resize((size_t)rows[i]);
-        vh.X.resize((size_t)rows[i]);
-        return pool.submit(rows[i], [&, i](int r) { phase1(i, vhits[i & 1], r); });
-    };
-    std::vector<Point> cloud;
-    {  // at most one point per pixel: reserve the address range once (pages
-       // are committed as points arrive), no reallocation copies in the walk
-        size_t cap = 0;
-        for (size_t i = 0; i < n; ++i) cap += (size_t)cols[i] * rows[i];
-        cloud.reserve(cap);
-    }
-    const auto t_loaded = now();
-    auto job = start_phase1(0);
+    std::vector<Point> cloud;  // reserved once (pages are committed as points arrive): no copies in the walk
+    cloud.reserve(sc.pixels());
+    ViewHits vhits[2];
+    WalkStats stats;
+    const auto t_loaded = Clock::now();
+    InFlight job{pool, nullptr};  // declared after all its rows touch: sc, vhits
+    job.start(sc, 0, vhits[0]);
     for (size_t i = 0; i < n; ++i) {
-        const int W = cols[i], H = rows[i];
-        const int num_ngb = problems[i].num_src_images;
+        const int W = sc.cols[i], H = sc.rows[i];
         std::vector<uint8_t> approved(write_debug_images ? (size_t)W * H : 0, 0);
-        const auto t0 = now();
-        pool.wait(job);
-        const auto t1 = now();
-        t_wait += secs(t0, t1);
-        if (i + 1 < n) job = start_phase1(i + 1);
-        const ViewHits &vh = vhits[i & 1];
-        // per source: its mask words; used_list as mask indices (-1 unset)
-        std::vector<uint64_t *> mw((size_t)std::max(num_ngb, 1));
-        for (int j = 0; j < num_ngb; ++j) mw[(size_t)j] = masks[(size_t)src_index[i][j]].w.data();
-        std::vector<int64_t> used_sp((size_t)std::max(num_ngb, 1), -1);
-        uint32_t dirty = 0;  // used_sp entries written since the last approval
-        auto bit = [](const uint64_t *w, size_t k) -> bool {
-            return (__atomic_load_n(&w[k >> 6], __ATOMIC_RELAXED) >> (k & 63)) & 1ull;
-        };
-        constexpr uint32_t kSpMask = (1u << kSpBits) - 1;
-        for (int r = 0; r < H; ++r) {
-            const uint32_t *h = vh.hit[(size_t)r].data();
-            const float *hx = vh.ex[(size_t)r].data();
-            const std::vector<int> &lv = vh.live[(size_t)r];
-            const uint16_t *nhr = vh.nhit[(size_t)r].data();
-            const float *sumr = vh.sum[(size_t)r].data();
-            const F3 *xr = vh.X[(size_t)r].data();
-            const size_t nl = lv.size();
-            for (size_t k = 0; k < nl; ++k) {  // the pixels live in phase 1, in column order
-                const int c = lv[k];
-                const size_t pc = (size_t)r * W + c;
-                const int nh = nhr[k];
-                const uint32_t *hp = h;
-                const float *hxp = hx;
-                const F3 *xp = xr + k;
-                h += nh;
-                hx += nh;
-                // re-read: view i - 1's walk (beside view i's phase 1) and,
-                // if i is its own source, view i's own approvals set bits
-                if (masks[i].get(pc)) continue;
-                int num_consistent = 0;
-                bool masked = false;
-                for (int q = 0; q < nh; ++q) {
-                    const uint32_t j = hp[q] >> kSpBits, sp = hp[q] & kSpMask;
-                    if (bit(mw[j], sp)) {
-                        masked = true;
-                        continue;
-                    }
-                    used_sp[j] = sp;
-                    dirty |= 1u << j;
-                    num_consistent++;
-                }
-                float dynamic_consistency = sumr[k];
-                n_live++;
-                n_hits += (size_t)nh;
-                n_masked += masked;
-                if (masked) {  // re-add the unmasked ones, ascending j
-                    dynamic_consistency = 0;
-                    for (int q = 0; q < nh; ++q)
-                        if (!bit(mw[hp[q] >> kSpBits], hp[q] & kSpMask)) dynamic_consistency += hxp[q];
-                }
-                if (num_consistent >= con_num_thresh && (dynamic_consistency > consistency_scalar * num_consistent)) {
-                    const float *ref_normal = &normals[i][pc * 3];
-                    const uint8_t *bgr = &images[i][pc * 3];
-                    Point p;
-                    p.coord = *xp;  // world_point(c, r, depths[i][pc], cameras[i]), formed in phase 1
-                    p.normal = F3{ref_normal[0], ref_normal[1], ref_normal[2]};
-                    p.color = F3{(float)bgr[0], (float)bgr[1], (float)bgr[2]};
-                    cloud.push_back(p);
-                    // used_list is not reset per pixel in the reference: stale
-                    // entries apply too. An entry unchanged since the last
-                    // approval was set then (masks only go 0 -> 1), so only
-                    // the entries written since are applied.
-                    for (; dirty; dirty &= dirty - 1) {
-                        const int j = __builtin_ctz(dirty);
-                        const int64_t sp = used_sp[(size_t)j];
-                        const int s = src_index[i][j];
-                        masks[s].set((size_t)sp);
-                        if (write_debug_images) {
-                            // `approved` is this view's W x H image indexed by source coordinates (:1030)
-                            const int ux = (int)(sp % cols[s]), uy = (int)(sp / cols[s]);
-                            if (uy < H && ux < W) approved[(size_t)uy * W + ux] = 255;
-                        }
-                    }
-                }
-            }
-        }
-        t_walk += secs(t1, now());
+        const auto t0 = Clock::now();
+        job.wait();
+        const auto t1 = Clock::now();
+        if (i + 1 < n) job.start(sc, i + 1, vhits[(i + 1) & 1]);
+        walk_view(sc, i, vhits[i & 1], con_num_thresh, consistency_scalar, cloud,
+                  write_debug_images ? approved.data() : nullptr, stats);
+        stats.t_wait += secs(t0, t1);
+        stats.t_walk += secs(t1, Clock::now());
         if (write_debug_images) {
             const std::string dbg = dense + "/approved_pixels_cam_" + std::to_string(i) + ".png";
-            if (acmmp_internal_write_png(dbg.c_str(), W, H, 1, approved.data())) {
-                if (i + 1 < n) pool.wait(job);
+            if (acmmp_internal_write_png(dbg.c_str(), W, H, 1, approved.data()))
                 return ffail(ACMMP_ERR_IO, "cannot write %s", dbg.c_str());
-            }
         }
     }
     if (num_points) *num_points = (int)cloud.size();
-    const auto t_walked = now();
-    const int rc = store_ply(out + "/ACMMP_model.ply", cloud, &pool);
+    const auto t_walked = Clock::now();
+    rc = store_ply(out + "/ACMMP_model.ply", cloud, &pool);
     if (timing)
         std::fprintf(stderr,
                      "[RunFusion] load=%.2fs candidates_wait=%.2fs walk=%.2fs ply=%.2fs threads=%d "
                      "walked_pixels=%zu hits=%zu pixels_with_masked_hits=%zu points=%zu pinned=%d\n",
-                     secs(t_start, t_loaded), t_wait, t_walk, secs(t_walked, now()), pool.size() + 1, n_live,
-                     n_hits, n_masked, cloud.size(), (int)dom.pinned());
+                     secs(t_start, t_loaded), stats.t_wait, stats.t_walk, secs(t_walked, Clock::now()),
+                     pool.size() + 1, stats.n_live, stats.n_hits, stats.n_masked, cloud.size(), (int)dom.pinned());
     return rc;
 }
 
@@ -913,67 +957,28 @@ int acmmp_run_prior_aware_fusion(const char *dense_folder, const char *output_fo
         return ffail(ACMMP_ERR_ARG, "bad args");
     const std::string dense = dense_folder, out = output_folder, fus = fusion_folder;
     const size_t n = (size_t)count;
-    FusionInputs in;
-    in.cameras.resize(n);
-    in.depths.resize(n);
-    in.normals.resize(n);
-    in.pdepths.resize(n);
-    in.pnormals.resize(n);
-    in.rows.resize(n);
-    in.cols.resize(n);
-    std::vector<std::vector<uint8_t>> images(n), masks(n);
-    std::map<int, int> image_id_2_index;
+    FusionInputs in(problems, n);
+    std::vector<std::vector<uint8_t>> &images = in.images, masks(n);
     const char *suffix = geom_consistency ? "/depths_geom.dmb" : "/depths.dmb";
     for (size_t i = 0; i < n; ++i) {
         const int id = problems[i].ref_image_id;
-        image_id_2_index[id] = (int)i;
-        const std::string ipath = dense + "/images/" + id8(id) + ".jpg";
-        int iw = 0, ih = 0;
-        std::vector<uint8_t> img;
-        int rc = acmmp_internal_read_image_bgr(ipath.c_str(), img, iw, ih);
-        if (rc) return ffail(rc, "cannot read image %s", ipath.c_str());
-        const std::string cpath = camera_path(dense, id);
-        if (acmmp_read_camera(cpath.c_str(), &in.cameras[i]))
-            return ffail(ACMMP_ERR_IO, "cannot read %s", cpath.c_str());
         // maps of the other reconstruction (fusion_folder) and of this run's (output_folder) priors
-        const std::string rf = result_folder(fus, id), pf = result_folder(out, id);
-        int h, w, nb, h2, w2, nb2, h3, w3, nb3, h4, w4, nb4;
-        rc = read_dmb(rf + suffix, in.depths[i], h, w, nb);
-        if (!rc) rc = read_dmb(rf + "/normals.dmb", in.normals[i], h2, w2, nb2);
-        if (!rc) rc = read_dmb(pf + suffix, in.pdepths[i], h3, w3, nb3);
-        if (!rc) rc = read_dmb(pf + "/normals.dmb", in.pnormals[i], h4, w4, nb4);
+        int rc = load_view(in, i, dense + "/images", dense, result_folder(fus, id), suffix);
+        int h = 0, w = 0;
+        if (!rc) rc = read_maps(result_folder(out, id), suffix, id, in.pdepths[i], in.pnormals[i], h, w);
         if (rc) return rc;
-        if (nb != 1 || nb2 != 3 || nb3 != 1 || nb4 != 3 || h2 != h || w2 != w || h3 != h || w3 != w || h4 != h ||
-            w4 != w)
-            return ffail(ACMMP_ERR_IO, "map sizes of view %d disagree", id);
-        in.rows[i] = h;
-        in.cols[i] = w;
-        if (w == iw && h == ih) {
-            images[i] = std::move(img);
-        } else {
-            const float scale_x = w / static_cast<float>(iw);
-            const float scale_y = h / static_cast<float>(ih);
-            resize_u8(img, iw, ih, 3, images[i], w, h);
-            in.cameras[i].K[0] *= scale_x;
-            in.cameras[i].K[2] *= scale_x;
-            in.cameras[i].K[4] *= scale_y;
-            in.cameras[i].K[5] *= scale_y;
-        }
+        if (h != in.rows[i] || w != in.cols[i]) return ffail(ACMMP_ERR_IO, "map sizes of view %d disagree", id);
         // mask files give 255/0 here (:654-661), never the 1 the checks test:
         // only approvals mask pixels
         masks[i].assign((size_t)w * h, 0);
     }
+    const int src_rc = resolve_sources(in);
+    if (src_rc) return src_rc;
     std::vector<Point> cloud;
-    {  // at most one point per pixel (see RunFusion)
-        size_t cap = 0;
-        for (size_t i = 0; i < n; ++i) cap += (size_t)in.cols[i] * in.rows[i];
-        cloud.reserve(cap);
-    }
+    cloud.reserve(in.pixels());  // at most one point per pixel (see RunFusion)
     Pool pool;
-    // Same two-phase scheme as RunFusion: candidates (projection + metrics of
-    // both maps) per band of rows on host threads against the current masks,
-    // then the reference's pixel order with every approval re-checked
-    // against the masks as they stand then (they only ever go 0 -> 1).
+    // RunFusion's two steps per band of rows: candidates (projection + metrics of both maps) on host
+    // threads against the current masks, then the reference's pixel order with every approval re-checked
     struct Ok {  // a below-threshold candidate: the only kind that counts or masks
         int im, x, y;
         float dc;
@@ -981,12 +986,7 @@ int acmmp_run_prior_aware_fusion(const char *dense_folder, const char *output_fo
     const int band = 32;
     for (size_t i = 0; i < n; ++i) {
         const int W = in.cols[i], H = in.rows[i];
-        std::vector<int> srcs;
-        for (int j = 0; j < problems[i].num_src_images; ++j) {
-            auto it = image_id_2_index.find(problems[i].src_image_ids[j]);
-            if (it == image_id_2_index.end()) return ffail(ACMMP_ERR_ARG, "source is not a problem");
-            srcs.push_back(it->second);
-        }
+        const std::vector<int> &srcs = in.src_index[i];
         const int ns = std::max((int)srcs.size(), 1);
         // per pixel: bit 0 live, bit 1 map 0 evaluated, bit 2 map 1 evaluated
         std::vector<uint8_t> state((size_t)band * W);

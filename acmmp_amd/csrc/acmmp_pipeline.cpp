@@ -123,15 +123,7 @@ int load_image(const std::string &path, acmmp::Image &im) {
 }
 
 int read_dmb(const std::string &path, std::vector<float> &data, int &h, int &w, int &nb) {
-    int32_t hh = 0, ww = 0, bb = 0;
-    int rc = acmmp_read_dmb(path.c_str(), &hh, &ww, &bb, nullptr, 0);
-    if (rc != ACMMP_OK && rc != ACMMP_ERR_ARG) return fail(ACMMP_ERR_IO, "cannot read %s", path.c_str());
-    data.resize((size_t)hh * ww * bb);
-    rc = acmmp_read_dmb(path.c_str(), &hh, &ww, &bb, data.data(), data.size());
-    if (rc) return fail(ACMMP_ERR_IO, "cannot read %s", path.c_str());
-    h = hh;
-    w = ww;
-    nb = bb;
+    if (acmmp_hostio::read_dmb(path, data, h, w, nb)) return fail(ACMMP_ERR_IO, "cannot read %s", path.c_str());
     return ACMMP_OK;
 }
 
@@ -221,10 +213,7 @@ int load_view(const std::string &dense, int id, int max_image_size, acmmp::Image
     scaled.data.resize((size_t)new_cols * new_rows);
     acmmp_resize_linear(im.data.data(), im.cols, im.rows, scaled.data.data(), new_cols, new_rows);
     im = std::move(scaled);
-    cam.K[0] *= scale_x;
-    cam.K[2] *= scale_x;
-    cam.K[4] *= scale_y;
-    cam.K[5] *= scale_y;
+    scale_intrinsics(cam, scale_x, scale_y);
     cam.height = new_rows;
     cam.width = new_cols;
     return ACMMP_OK;
@@ -238,10 +227,8 @@ std::string prior_path(const std::string &dense, const char *kind, int cam) {
 }
 
 bool read_png(const std::string &path, std::vector<uint16_t> &px, int &w, int &h, int &c) {
-    int bd = 0;
-    if (acmmp_read_png(path.c_str(), nullptr, 0, &w, &h, &c, &bd) != ACMMP_ERR_ARG) return false;
-    px.resize((size_t)w * h * c);
-    return acmmp_read_png(path.c_str(), px.data(), px.size(), &w, &h, &c, &bd) == ACMMP_OK;
+    int bit_depth = 0;
+    return acmmp_hostio::read_png(path, px, w, h, c, bit_depth) == ACMMP_OK;
 }
 
 // depth_normal_to_plane (:72-89) with getViewDirection, normVec3 (which

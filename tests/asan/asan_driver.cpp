@@ -15,8 +15,10 @@
 //   asan_driver resize <iters> <seed>          acmmp_resize_linear
 //   asan_driver fusion <dense> <out> <fusion_folder | -> <ref:src,src,...>...
 //                      (a fusion folder = RunPriorAwareFusion, - = RunFusion)
+//   asan_driver fusion_fails <same arguments>  the fusion must return an error status
 //   asan_driver oracle <seed>                  CPU oracle RunPatchMatch branches, JBU, planar
-// Exit 0 = every call returned (any status); sanitizer findings abort.
+// Exit 0 = every call returned (any status; fusion: ACMMP_OK, fusion_fails:
+// another status); sanitizer findings abort.
 #include <unistd.h>
 
 #include <cstdint>
@@ -199,7 +201,7 @@ int fuzz_resize(int iters) {
     return 0;
 }
 
-int run_fusion(int argc, char **argv) {
+int run_fusion(int argc, char **argv, bool expect_failure) {
     if (argc < 6) return 2;
     const bool prior_aware = std::strcmp(argv[4], "-") != 0;
     std::vector<acmmp_problem> probs;
@@ -224,7 +226,7 @@ int run_fusion(int argc, char **argv) {
         rc = acmmp_run_fusion(argv[2], argv[3], probs.data(), (int)probs.size(), 1, 0.3f, 1, "/images", " ", 1,
                               &npts);
     std::printf("fusion rc=%d points=%d\n", rc, npts);
-    return rc == ACMMP_OK ? 0 : 3;
+    return (rc != ACMMP_OK) == expect_failure ? 0 : 3;
 }
 
 // a small textured scene on a sideways arc for the oracle
@@ -359,8 +361,8 @@ int main(int argc, char **argv) {
     } else if (cmd == "resize" && argc >= 3) {
         seed_at(3);
         rc = fuzz_resize(std::atoi(argv[2]));
-    } else if (cmd == "fusion") {
-        rc = run_fusion(argc, argv);
+    } else if (cmd == "fusion" || cmd == "fusion_fails") {
+        rc = run_fusion(argc, argv, cmd == "fusion_fails");
     } else if (cmd == "oracle") {
         seed_at(2);
         rc = run_oracle();

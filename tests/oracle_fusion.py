@@ -66,23 +66,64 @@ def _initial_mask(dense, mask_folder, ref_id, shape):
     return (rows[:, :W] < 128).astype(np.uint8)
 
 
-def run_fusion(dense, out, geom=True, consistency_scalar=0.3, con_num_thresh=1, mask_folder=None):
+def _resize_u8(src, dw, dh):
+    """The project's stand-in for cv::resize on 8-bit images (DESIGN.md §7):
+    float bilinear, half-pixel centres, edge clamp, nearbyint."""
+    sh, sw = src.shape[:2]
+
+    def taps(nd, ns):  # the position in double, then float
+        f = ((np.arange(nd) + 0.5) * ns / nd - 0.5).astype(f32)
+        i0 = np.floor(f).astype(np.int64)
+        a = f - i0.astype(f32)
+        for edge, at in ((i0 < 0, 0), (i0 >= ns - 1, ns - 1)):
+            i0[edge], a[edge] = at, 0
+        return i0, np.minimum(i0 + 1, ns - 1), a
+
+    y0, y1, ay = taps(dh, sh)
+    x0, x1, ax = taps(dw, sw)
+    s, ax, ay = src.astype(f32), ax[None, :, None], ay[:, None, None]
+    top = s[y0][:, x0] * (1 - ax) + s[y0][:, x1] * ax
+    bot = s[y1][:, x0] * (1 - ax) + s[y1][:, x1] * ax
+    return np.clip(np.rint(top * (1 - ay) + bot * ay), 0, 255).astype(np.uint8)
+
+
+def _load_view(dense, ref_id, shape):
+    """One view's BGR image and camera at its maps' size: RescaleImageAndCamera
+    (src/ACMMP.cpp:181-201), K rows 0 and 1 scaled in float."""
     from PIL import Image
+    rgb = np.asarray(Image.open(os.path.join(dense, "images", "%08d.jpg" % ref_id)).convert("RGB"))
+    bgr = rgb[..., ::-1]
+    cam = aio.read_camera(os.path.join(dense, "cams", "%08d_cam.txt" % ref_id))
+    (h, w), (ih, iw) = shape, bgr.shape[:2]
+    if (w, h) != (iw, ih):
+        bgr = _resize_u8(bgr, w, h)
+        sx, sy = f32(w) / f32(iw), f32(h) / f32(ih)
+        for k, s in ((0, sx), (2, sx), (4, sy), (5, sy)):
+            cam.K[k] = float(f32(cam.K[k]) * s)
+    return bgr, cam
+
+
+def run_fusion(dense, out, geom=True, consistency_scalar=0.3, con_num_thresh=1, mask_folder=None,
+               debug_images=False):
+    """Returns the cloud; with debug_images, (cloud, per view its `approved`
+    image: 255 at every applied used_list entry that falls inside the view's
+    own W x H, :1030 -- the entries are source coordinates)."""
     problems = aio.read_pair(os.path.join(dense, "pair.txt"))
     index = {p.ref_image_id: i for i, p in enumerate(problems)}
     imgs, cams, depths, normals, masks = [], [], [], [], []
     for p in problems:
-        rgb = np.asarray(Image.open(os.path.join(dense, "images", "%08d.jpg" % p.ref_image_id)).convert("RGB"))
-        imgs.append(rgb[..., ::-1])
-        cams.append(aio.read_camera(os.path.join(dense, "cams", "%08d_cam.txt" % p.ref_image_id)))
         rf = aio.result_folder(out, p.ref_image_id)
         depths.append(aio.read_dmb(os.path.join(rf, "depths_geom.dmb" if geom else "depths.dmb")))
         normals.append(aio.read_dmb(os.path.join(rf, "normals.dmb")))
+        img, cam = _load_view(dense, p.ref_image_id, depths[-1].shape)
+        imgs.append(img)
+        cams.append(cam)
         masks.append(np.zeros(depths[-1].shape, np.uint8) if mask_folder is None else
                      _initial_mask(dense, mask_folder, p.ref_image_id, depths[-1].shape))
-    cloud = []
+    cloud, approved = [], []
     for i, p in enumerate(problems):
         H, W = depths[i].shape
+        approved.append(np.zeros((H, W), np.uint8))
         srcs = [index[s] for s in p.src_image_ids]
         used = [(-1, -1)] * len(srcs)
         depth_max = f32(cams[i].depth_max)
@@ -126,7 +167,9 @@ def run_fusion(dense, out, geom=True, consistency_scalar=0.3, con_num_thresh=1, 
                         if used[j][0] == -1:
                             continue
                         masks[s][used[j][1], used[j][0]] = 1
-    return cloud
+                        if used[j][1] < H and used[j][0] < W:
+                            approved[i][used[j][1], used[j][0]] = 255
+    return (cloud, approved) if debug_images else cloud
 
 
 def read_ply(path):
@@ -167,20 +210,19 @@ def _cmetrics(i, r, c, ref_depth, ref_normal, cams, s, src_r, src_c, maps):
 def run_prior_aware_fusion(dense, out, fusion_folder, geom=True, consistency_scalar=0.3, con_num_thresh=1,
                            penalty=0):
     """RunPriorAwareFusion (src/acmmp_definitions.cpp:573-826) restated."""
-    from PIL import Image
     problems = aio.read_pair(os.path.join(dense, "pair.txt"))
     index = {p.ref_image_id: i for i, p in enumerate(problems)}
     suffix = "depths_geom.dmb" if geom else "depths.dmb"
     imgs, cams, depths, normals, pdepths, pnormals, masks = [], [], [], [], [], [], []
     for p in problems:
-        rgb = np.asarray(Image.open(os.path.join(dense, "images", "%08d.jpg" % p.ref_image_id)).convert("RGB"))
-        imgs.append(rgb[..., ::-1])
-        cams.append(aio.read_camera(os.path.join(dense, "cams", "%08d_cam.txt" % p.ref_image_id)))
         rf, pf = aio.result_folder(fusion_folder, p.ref_image_id), aio.result_folder(out, p.ref_image_id)
         depths.append(aio.read_dmb(os.path.join(rf, suffix)))
         normals.append(aio.read_dmb(os.path.join(rf, "normals.dmb")))
         pdepths.append(aio.read_dmb(os.path.join(pf, suffix)))
         pnormals.append(aio.read_dmb(os.path.join(pf, "normals.dmb")))
+        img, cam = _load_view(dense, p.ref_image_id, depths[-1].shape)
+        imgs.append(img)
+        cams.append(cam)
         masks.append(np.zeros(depths[-1].shape, np.uint8))
     maps = (depths, normals, pdepths, pnormals)
     cloud = []

@@ -112,3 +112,8 @@ def test_fusion_and_prior_aware_fusion(driver, tmp_path):
         for name in ("depths_geom.dmb", "normals.dmb"):
             shutil.copy(os.path.join(src, name), os.path.join(dst, name))
     assert "points=" in run([driver, "fusion", d, prior, out] + probs, cwd=tmp_path)
+    # RunFusion returning early (view 0's debug image cannot be written: its
+    # name is a directory) while view 1's candidate job is in flight on the pool
+    os.remove(os.path.join(d, "approved_pixels_cam_0.png"))  # the first run's
+    os.makedirs(os.path.join(d, "approved_pixels_cam_0.png"))
+    assert "fusion rc=-4" in run([driver, "fusion_fails", d, out, "-"] + probs, cwd=tmp_path)

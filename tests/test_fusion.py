@@ -7,8 +7,10 @@ import os
 import numpy as np
 import pytest
 
+from acmmp_amd import _abi
 from acmmp_amd import io as aio
 from acmmp_amd import pipeline, scene
+from acmmp_amd.engine import AcmmpError
 from oracle_fusion import read_ply, run_fusion
 
 
@@ -141,10 +143,8 @@ def _compare_cloud(ply, ref):
     np.testing.assert_array_equal(np.stack([ply["r"], ply["g"], ply["b"]], -1), col)
 
 
-def test_prior_aware_fusion_matches_python_restatement(tmp_path):
-    from oracle_fusion import run_prior_aware_fusion
-    d, out = _dense_with_maps(tmp_path)
-    # a second reconstruction (the "prior" run's output folder) with perturbed maps
+def _prior_reconstruction(d, out):
+    """A second reconstruction (the "prior" run's output folder): `out`'s maps, perturbed."""
     prior = d + "/ACMMP_PRIOR"
     rng = np.random.default_rng(2)
     for i in range(4):
@@ -155,9 +155,140 @@ def test_prior_aware_fusion_matches_python_restatement(tmp_path):
         dep[rng.random(dep.shape) < 0.1] = 0.0
         aio.write_dmb(os.path.join(dst, "depths_geom.dmb"), dep)
         aio.write_dmb(os.path.join(dst, "normals.dmb"), aio.read_dmb(os.path.join(src, "normals.dmb")))
+    return prior
+
+
+def test_prior_aware_fusion_matches_python_restatement(tmp_path):
+    from oracle_fusion import run_prior_aware_fusion
+    d, out = _dense_with_maps(tmp_path)
+    prior = _prior_reconstruction(d, out)
     for penalty in (0, 1):
         n = pipeline.run_prior_aware_fusion(d, prior, out, single_match_penalty=penalty)
         ply = read_ply(os.path.join(prior, "ACMMP_prior_model.ply"))
         ref = run_prior_aware_fusion(d, prior, out, penalty=penalty)
         assert n > 500
         _compare_cloud(ply, ref)
+
+
+# ---- views whose image, maps and neighbours differ in size: RescaleImageAndCamera
+# (src/ACMMP.cpp:181-201) in both fusions, and sources of another size than the view
+
+def _shrink_maps_of_view_1(d, out):
+    """View 1's maps at 60x45 (nearest sampling) under its 72x54 image and
+    camera; the other views then see a source of another size."""
+    rows = np.minimum(((np.arange(45) + 0.5) * 54 / 45).astype(int), 53)
+    cols = np.minimum(((np.arange(60) + 0.5) * 72 / 60).astype(int), 71)
+    for name in ("depths_geom.dmb", "normals.dmb"):
+        path = os.path.join(aio.result_folder(out, 1), name)
+        aio.write_dmb(path, aio.read_dmb(path)[rows][:, cols])
+
+
+def _enlarge_images(d, out):
+    """All four colour images at 100x75 over 72x54 maps, K rows 0 and 1 of the
+    cam files scaled to match."""
+    from PIL import Image
+    for i in range(4):
+        path = os.path.join(d, "images", "%08d.jpg" % i)
+        Image.open(path).convert("RGB").resize((100, 75), Image.BILINEAR).save(path, "JPEG", quality=92)
+        cam = os.path.join(d, "cams", "%08d_cam.txt" % i)
+        lines = open(cam).read().split("\n")
+        k = lines.index("intrinsic")
+        for row, s in ((k + 1, 100 / 72), (k + 2, 75 / 54)):
+            lines[row] = " ".join(repr(float(v) * s) for v in lines[row].split()) + " "
+        open(cam, "w").write("\n".join(lines))
+
+
+@pytest.mark.parametrize("resized", [_shrink_maps_of_view_1, _enlarge_images])
+def test_fusions_rescale_image_and_camera_to_the_maps(tmp_path, resized):
+    from oracle_fusion import run_prior_aware_fusion
+    d, out = _dense_with_maps(tmp_path)
+    resized(d, out)
+    n = pipeline.run_fusion(d, out)
+    ref = run_fusion(d, out)
+    print("RunFusion points:", n)
+    assert n > 1000
+    _compare_cloud(read_ply(os.path.join(out, "ACMMP_model.ply")), ref)
+    prior = _prior_reconstruction(d, out)
+    n = pipeline.run_prior_aware_fusion(d, prior, out)
+    ref = run_prior_aware_fusion(d, prior, out)
+    print("RunPriorAwareFusion points:", n)
+    assert n > 500
+    _compare_cloud(read_ply(os.path.join(prior, "ACMMP_prior_model.ply")), ref)
+
+
+@pytest.mark.parametrize("mixed_sizes", [False, True])
+def test_fusion_debug_images_match_restatement(tmp_path, mixed_sizes):
+    """approved_pixels_cam_<i>.png: view i's W x H image, 255 at the source
+    coordinates of every applied used_list entry that falls inside it (:1030)."""
+    from PIL import Image
+    d, out = _dense_with_maps(tmp_path)
+    if mixed_sizes:
+        _shrink_maps_of_view_1(d, out)
+    pipeline.run_fusion(d, out, write_debug_images=True)
+    _, approved = run_fusion(d, out, debug_images=True)
+    for i, ref in enumerate(approved):
+        got = np.asarray(Image.open(os.path.join(d, "approved_pixels_cam_%d.png" % i)))
+        print("view", i, "approved pixels:", int((ref == 255).sum()))
+        assert (ref == 255).sum() > 100
+        np.testing.assert_array_equal(got, ref)
+
+
+# ---- statuses: the number AcmmpError prints, and that the message names the file or view
+
+def _status(err, code):
+    return "(status %d)" % code in str(err.value)
+
+
+@pytest.mark.parametrize("prior_aware", [False, True])
+def test_fusion_source_that_is_no_problem_is_err_arg(tmp_path, prior_aware):
+    d, out = _dense_with_maps(tmp_path)
+    problems = pipeline.generate_sample_list(d)[:3]  # view 3 stays a source of the others
+    assert any(3 in list(p.src_image_ids[:p.num_src_images]) for p in problems)
+    with pytest.raises(AcmmpError) as err:
+        if prior_aware:
+            pipeline.run_prior_aware_fusion(d, out, out, problems=problems)
+        else:
+            pipeline.run_fusion(d, out, problems=problems)
+    assert _status(err, _abi.ERR_ARG)
+    if not prior_aware:  # (the prior-aware fusion's message named nothing before it shared resolve_sources)
+        assert "source 3 of view" in str(err.value)
+
+
+def test_fusion_missing_or_mismatched_normals_are_err_io(tmp_path):
+    d, out = _dense_with_maps(tmp_path)
+    normals = os.path.join(aio.result_folder(out, 2), "normals.dmb")
+    nrm = aio.read_dmb(normals)
+    aio.write_dmb(normals, nrm[:50])
+    with pytest.raises(AcmmpError) as err:
+        pipeline.run_fusion(d, out)
+    assert _status(err, _abi.ERR_IO) and "view 2" in str(err.value)
+    os.remove(normals)
+    with pytest.raises(AcmmpError) as err:
+        pipeline.run_fusion(d, out)
+    assert _status(err, _abi.ERR_IO) and normals in str(err.value)
+
+
+def test_fusion_mask_errors(tmp_path):
+    from PIL import Image
+    d, out = _dense_with_maps(tmp_path)
+    os.makedirs(os.path.join(d, "masks"))
+    for i in range(3):  # view 3's mask is missing
+        Image.fromarray(np.full((54, 72), 255, np.uint8), "L").save(os.path.join(d, "masks", "%08d.png" % i))
+    with pytest.raises(AcmmpError) as err:
+        pipeline.run_fusion(d, out, mask_folder="masks")
+    assert _status(err, _abi.ERR_IO) and "masks/00000003.png" in str(err.value)
+    # a 16-bit mask of another size than the maps: its resize is not defined here
+    Image.fromarray(np.full((30, 40), 300, np.uint16)).save(os.path.join(d, "masks", "00000003.png"))
+    with pytest.raises(AcmmpError) as err:
+        pipeline.run_fusion(d, out, mask_folder="masks")
+    assert _status(err, _abi.ERR_UNSUPPORTED) and "masks/00000003.png" in str(err.value)
+
+
+def test_fusion_unwritable_debug_image_is_err_io(tmp_path):
+    """The first debug image cannot be written (its name is a directory): the
+    call returns while view 1's candidate job is in flight on the pool."""
+    d, out = _dense_with_maps(tmp_path)
+    os.makedirs(os.path.join(d, "approved_pixels_cam_0.png"))
+    with pytest.raises(AcmmpError) as err:
+        pipeline.run_fusion(d, out, write_debug_images=True)
+    assert _status(err, _abi.ERR_IO) and "approved_pixels_cam_0.png" in str(err.value)
