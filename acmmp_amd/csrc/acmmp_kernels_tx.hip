@@ -110,15 +110,23 @@ struct ViewCounts {
 // lane's slots may still hold live candidates of another wave's t = 0 step
 // — nothing may spill across lanes of different waves):
 //   slots 0..4 = the 5 refinement planes; slot 5 = results of planes 0..3;
-//   slot 6 = (result of plane 4, mean, var, inv_wsum); slot 7.x = the wave's
-//   owner list entry of this lane's rank.
+//   slot 6 = (result of plane 4, mean, var, inv_wsum); slots 7 of the wave's
+//   64 lanes (1024 contiguous bytes) = the wave's item list of one view.
 DEV float &cmp_res(float4 *lds, int t, int lane) {
     return reinterpret_cast<float *>(lds)[4 * ((5 + (t >> 2)) * kThreads + lane) + (t & 3)];
 }
 DEV float &cmp_pd(float4 *lds, int k, int lane) {  // k = 1 mean, 2 var, 3 inv_wsum
     return reinterpret_cast<float *>(lds)[4 * (6 * kThreads + lane) + k];
 }
-DEV int &cmp_list(float4 *lds, int lane) { return reinterpret_cast<int *>(lds)[4 * (7 * kThreads + lane)]; }
+// Item k of the wave whose first lane is wbase: (t << 6) | owner lane. At most
+// 5 * 64 = 320 items of 2 bytes (t = 4 does not fit a byte): 640 of the 1024.
+DEV uint16_t &cmp_item(float4 *lds, int wbase, int k) {
+    return reinterpret_cast<uint16_t *>(lds + 7 * kThreads + wbase)[k];
+}
+// Set bits of the wave mask m below this lane.
+DEV int rank_below(uint64_t m) {
+    return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
 
 DEV void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -132,15 +140,31 @@ DEV void wave_sync() {
 // sums are formed here, view-major, and the sequential accept of the caller
 // then consumes them in order t = 1..5 (same operations, same order per
 // (lane, t): j ascending). Instead of one pass per (t, view with any lane
-// sampling it), the wave packs the (owner lane, t) items of view j into
-// ceil(5 c_j / active lanes) passes, c_j = lanes that sampled j: a lane
-// evaluates another lane's item with that lane's pixel, LDS patch weights,
-// tile offset and plane, and returns the cost through LDS. The view stays
-// wave-uniform (scalar SRD and cameras). Result: cmp_res(t, lane) = sum_t.
+// sampling it), the wave packs the live (owner lane, t) items of view j into
+// ceil(items / active lanes) passes: a lane evaluates another lane's item
+// with that lane's pixel, LDS patch weights, tile offset and plane, and
+// returns the cost through LDS. The view stays wave-uniform (scalar SRD and
+// cameras). Result: cmp_res(t, lane) = sum_t, or a prefix of it (below).
+//
+// Dead hypotheses. Outside the planar-prior branch the caller uses sum_t only
+// in `sum_t / weight_norm < cost_now`, and cost_now only falls while it
+// consumes t = 1..5. Every term w_j * c_j is >= 0 or NaN (w_j >= 1, c_j an
+// NCC in [0, 2] plus 0.2 * a non-negative geometric cost), so the running sum
+// never decreases under round-to-nearest, and x / weight_norm is monotone in
+// x. With `bound` the lane's cost_now on entry: once a prefix satisfies
+// prefix / weight_norm >= bound, sum_t / weight_norm >= bound >= cost_now
+// holds for whatever the remaining views cost (or sum_t is NaN), and the
+// caller's comparison is false. Such a (lane, t) is dead: its remaining items
+// are not packed, and cmp_res(t, lane) is left at the prefix, for which the
+// caller's comparison is false by the same inequality. A NaN prefix or bound
+// makes the test false, so nothing is dropped there. Planar-prior lanes, whose
+// accept rule is another one, come with `prunable` false (a flag rather than
+// a NaN bound: the select's extra VGPR put the NS 9 kernel 16 B of scratch
+// over what tests/test_isa_guards.py allows).
 template <int TX, typename RD, typename RN>
 DEV void refine_costs_compact(const KViews &kv, const float *tile, WSlot *wlds, float4 *lds, const PixPatch &pp,
                               const ViewCounts &vw, int nsrc, int colour, BlockXY blk, RD ref_depth,
-                              RN ref_normal, int px, int py) {
+                              RN ref_normal, int px, int py, float weight_norm, float bound, bool prunable) {
     const acmmp_camera &c0 = kv.cam[0];
     const int tid = pp.wo;
 #pragma unroll
@@ -153,24 +177,37 @@ DEV void refine_costs_compact(const KViews &kv, const float *tile, WSlot *wlds, 
     cmp_pd(lds, 2, tid) = pp.var;
     cmp_pd(lds, 3, tid) = pp.inv_wsum;
     const int lane = tid & 63, wbase = tid & ~63;
-    const uint64_t lt = (1ull << lane) - 1ull;
     const uint64_t act = __ballot(1);
-    const int nact = __popcll(act), arank = __popcll(act & lt);
+    const int nact = __popcll(act), arank = rank_below(act);
     float acc[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    uint32_t alive = 31u;  // bit t: hypothesis t of this lane can still win
     wave_sync();
     for (int j = 0; j < nsrc; ++j) {
         const float wj = (float)vw.get(j);
-        const uint64_t m = __ballot(wj > 0);
-        if (m == 0) continue;
-        const int c = __popcll(m);
-        if (wj > 0) cmp_list(lds, wbase + __popcll(m & lt)) = lane;
+        // the view's items, t-major: every count and offset comes from a
+        // ballot, so the pass loop and the wave_sync()s stay wave-uniform
+        uint64_t mt[5];
+        int off[6];
+        off[0] = 0;
+#pragma unroll
+        for (int t = 0; t < 5; ++t) {
+            mt[t] = __ballot(wj > 0 && ((alive >> t) & 1u));
+            off[t + 1] = off[t] + __popcll(mt[t]);
+        }
+        const int n = off[5];
+        if (n == 0) continue;
+        if (wj > 0) {
+#pragma unroll
+            for (int t = 0; t < 5; ++t)
+                if ((alive >> t) & 1u) cmp_item(lds, wbase, off[t] + rank_below(mt[t])) = (uint16_t)((t << 6) | lane);
+        }
         wave_sync();
-        const int n = 5 * c;
         for (int base = 0; base < n; base += nact) {
             const int k = base + arank;
             if (k < n) {
-                const int t = k / c;
-                const int otid = wbase + cmp_list(lds, wbase + (k - t * c));
+                const int item = cmp_item(lds, wbase, k);
+                const int t = item >> 6;
+                const int otid = wbase + (item & 63);
                 const LaneGeom og = lane_geom_of(colour, blk, otid);
                 PixPatch op;
                 op.wo = otid;
@@ -190,11 +227,20 @@ DEV void refine_costs_compact(const KViews &kv, const float *tile, WSlot *wlds, 
         }
         wave_sync();
         if (wj > 0) {
+            // (a dead t's result slot is stale: read, not used. The test is
+            // the caller's own expression, tc / weight_norm)
 #pragma unroll
-            for (int t = 0; t < 5; ++t) acc[t] += wj * cmp_res(lds, t, tid);
+            for (int t = 0; t < 5; ++t) {
+                const float a = acc[t] + wj * cmp_res(lds, t, tid);
+                const bool live = (alive >> t) & 1u;
+                acc[t] = live ? a : acc[t];
+                if (live && prunable && a / weight_norm >= bound) alive &= ~(1u << t);
+            }
         }
         wave_sync();
     }
+    // a dead t hands over its prefix: prefix / weight_norm >= bound >= the
+    // caller's cost_now, so `tc < cost_now` is false, as it is for the full sum
 #pragma unroll
     for (int t = 0; t < 5; ++t) cmp_res(lds, t, tid) = acc[t];
     wave_sync();
@@ -555,10 +601,14 @@ DEV void sweep_body(const KViews *__restrict__ kvp, KState st, int colour, int i
     const float beta = 0.18f;
 
     for (int t = 0; t < 6; ++t) {
-        // all 5 refinement costs at once (their planes go to LDS slots 0..4)
+        // all 5 refinement costs at once (their planes go to LDS slots 0..4).
+        // cost_now is final for t = 0 here and only falls from here on: it
+        // bounds what a refinement plane may cost and still be accepted. A
+        // planar-prior lane accepts by exp(-c^2 / beta) * prior instead and
+        // may raise cost_now: it keeps all its hypotheses
         if (t == 1)
             refine_costs_compact<TX>(kv, tile, wlds, cand_lds, pp, vw, nsrc, colour, blk, ref_depth, ref_normal,
-                                     px, py);
+                                     px, py, weight_norm, cost_now, !has_prior);
         float4 h;
         if (t == 0) h = my_plane;
         else h = cand_lds[(t - 1) * kThreads + pp.wo];  // stored by refine_costs_compact
