@@ -4,7 +4,8 @@
 // all-gather per pass. The same schedule as the Python driver
 // (acmmp_amd/distributed.py), so the .dmb outputs are bit-identical to it:
 //
-//   * sharding: LPT on W*H*(N-1) of the full-size reference image;
+//   * sharding: LPT on W*H*(N-1) of the full-size reference image (the
+//     placement, the band rows and the all-gather slots: acmmp_vp_plan.h);
 //   * per scale (src/main_ACMMP.cpp:96-176): the images every owned view
 //     needs are decoded once (acmmp_load_view) and kept in HBM; the first
 //     scale runs the photometric + planar-prior pass, finer scales JBU +
@@ -54,7 +55,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
-#include <mutex>
 #include <stdexcept>
 #include <string>
 #include <thread>
@@ -63,10 +63,12 @@
 #include "../../include/acmmp.h"
 #include "acmmp_dense.h"
 #include "acmmp_vp.h"
+#include "acmmp_vp_plan.h"
 
 namespace {
 
 using namespace acmmp_dense;
+using namespace acmmp_vp;
 
 struct Fail : std::runtime_error {
     using std::runtime_error::runtime_error;
@@ -326,64 +328,74 @@ struct DevBuf {
 
 struct ViewState {
     DevBuf planes, costs;  // (H, W, 4) world normal + depth, (H, W)
+    DevBuf depth;          // (H, W): the planes' depth channel, what the next pass's gather and JBU read
     int W = 0, H = 0;
     DevBuf jbu;  // upsampled depth of the hierarchy pass (device, the next scale's W x H)
+    ViewState() = default;
+    ViewState(int w, int h) : planes((size_t)w * h * 4), costs((size_t)w * h), depth((size_t)w * h), W(w), H(h) {}
+};
+
+// Rows [lo, hi) of a device map of `row_floats` floats per row, to (pack) or
+// from a contiguous block, on `cs`.
+void copy_rows(void *map, size_t row_floats, int lo, int hi, float *block, bool pack, hipStream_t cs) {
+    const size_t n = (size_t)(hi - lo) * row_floats;
+    if (!n) return;
+    float *rows = static_cast<float *>(map) + (size_t)lo * row_floats;
+    hip_check(hipMemcpyAsync(pack ? block : rows, pack ? rows : block, n * sizeof(float), hipMemcpyDeviceToDevice, cs),
+              "hipMemcpyAsync");
+}
+
+// One padded all-gather of a map per view (acmmp_vp_plan.h's GatherLayout):
+// the zero-filled send buffer with this rank's views in its slots, and the
+// gathered buffer every view's map is borrowed from in place.
+class PaddedGather {
+  public:
+    PaddedGather() = default;
+    PaddedGather(const Plan &plan, int hmax, int wmax)
+        : at_{&plan, hmax, wmax}, send_(at_.send_floats()), recv_(at_.recv_floats()) {
+        hip_check(hipMemset(send_.p, 0, send_.n * sizeof(float)), "hipMemset");
+    }
+    // view v (one of this rank's) = the contiguous w x h device map
+    void put(int v, const float *map, int w, int h) {
+        hip_check(hipMemcpy2D(send_.p + at_.send_offset(v), (size_t)at_.wmax * sizeof(float), map,
+                              (size_t)w * sizeof(float), (size_t)w * sizeof(float), (size_t)h,
+                              hipMemcpyDeviceToDevice),
+                  "hipMemcpy2D");
+    }
+    // every rank's views on every rank (the puts above are complete first)
+    void gather(Exchange &ex) {
+        hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+        ex.allgather(send_.p, recv_.p, send_.n);
+    }
+    void drop_send() { send_ = DevBuf(); }  // nothing more is put in
+    // view v's gathered map, rows pitch() floats apart
+    const float *map(int v) const { return recv_.p + at_.recv_offset(v); }
+    int pitch() const { return at_.wmax; }
+
+  private:
+    GatherLayout at_;
+    DevBuf send_, recv_;
+};
+
+// One pass of the schedule over every view (src/main_ACMMP.cpp:96-176)
+struct Pass {
+    bool geom, planar, hier, multi;
+    // the first scale: photometric, then again with the planar prior (:109-120)
+    static Pass planar_prior() { return {false, true, false, false}; }
+    // a finer scale, after JBU: the same from the upsampled previous scale (:146-155)
+    static Pass hierarchy() { return {false, true, true, false}; }
+    // geometric consistency; every one after a scale's first is multi-geometry (:121-138, :156-173)
+    static Pass geometric(bool multi) { return {true, false, false, multi}; }
 };
 
 // --------------------------------------------------------------- driver
 class Driver {
   public:
-    Driver(const VpOptions &o, Group &g) : o_(o), g_(g), ex_(g, o.exchange_rccl, o.device) {
-        output_folder_ = o.dense + o.output_dir;
-        problems_.resize(4096);
-        int n = 0;
-        acmmp_check(acmmp_generate_sample_list(o.dense.c_str(), problems_.data(), (int)problems_.size(), &n),
-                    "GenerateSampleList");
-        problems_.resize((size_t)n);
-        acmmp_check(acmmp_compute_multiscale_settings(o.dense.c_str(), problems_.data(), n, &max_down_),
-                    "ComputeMultiScaleSettings");
-        for (int i = 0; i < n; ++i) index_of_[problems_[(size_t)i].ref_image_id] = i;
-        // LPT on W*H*max(N-1, 1) of the full-size reference image
-        std::vector<double> cost((size_t)n);
-        for (int i = 0; i < n; ++i) {
-            int w = 0, h = 0;
-            acmmp_check(acmmp_view_size(o.dense.c_str(), problems_[(size_t)i].ref_image_id, 0, &w, &h), "image header");
-            cost[(size_t)i] = (double)w * h * std::max(problems_[(size_t)i].num_src_images, 1);
-        }
-        std::vector<int> order((size_t)n);
-        for (int i = 0; i < n; ++i) order[(size_t)i] = i;
-        std::sort(order.begin(), order.end(), [&](int a, int b) {
-            return cost[(size_t)a] != cost[(size_t)b] ? cost[(size_t)a] > cost[(size_t)b] : a < b;
-        });
-        // the tail (V mod world cheapest views) is split over all ranks;
-        // the rest LPT; each split view's owner is the least loaded rank
-        const int ntail = (o.split_tail && g.world > 1) ? n % g.world : 0;
-        split_.assign(order.end() - ntail, order.end());
-        std::sort(split_.begin(), split_.end());
-        std::vector<double> load((size_t)g.world, 0.0);
-        assignment_.assign((size_t)g.world, {});
-        auto place = [&](int v) {
-            int r = 0;
-            for (int k = 1; k < g.world; ++k)
-                if (load[(size_t)k] < load[(size_t)r]) r = k;
-            assignment_[(size_t)r].push_back(v);
-            load[(size_t)r] += cost[(size_t)v];
-        };
-        for (int v : order)
-            if (!is_split(v)) place(v);
-        for (int v : split_) place(v);
-        for (auto &a : assignment_) std::sort(a.begin(), a.end());
-        owned_ = assignment_[(size_t)g.rank];
-        for (int v : owned_)
-            if (!is_split(v)) mine_.push_back(v);
-        for (int k = 0; k < std::max(o.concurrent_views, 1); ++k) {
-            acmmp_ctx *ctx = nullptr;
-            acmmp_check(acmmp_create(o.device, &ctx), "acmmp_create");
-            engines_.push_back(ctx);
-            hipStream_t cs = nullptr;
-            hip_check(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking), "hipStreamCreate");
-            copy_.push_back(cs);
-        }
+    Driver(const VpOptions &o, Group &g)
+        : o_(o), g_(g), ex_(g, o.exchange_rccl, o.device), output_folder_(o.dense + o.output_dir) {
+        read_problems();
+        plan();
+        create_engines();
     }
 
     ~Driver() {
@@ -401,20 +413,22 @@ class Driver {
             scale_step(problems_.data(), (int)problems_.size());
             {
                 Clock c(this, "load");
-                shapes();
+                read_shapes();
+                if (first) plan_.apply_halo_rule(height_);  // the coarsest scale decides which views stay split
+                depths_ = PaddedGather(plan_, hmax_, wmax_);
                 load_views();
             }
             if (first) {
                 first = false;
-                run_pass(false, true, false, false);
+                run_pass(Pass::planar_prior());
             } else {
                 {
                     Clock c(this, "jbu");
                     jbu();
                 }
-                run_pass(false, true, true, false);
+                run_pass(Pass::hierarchy());
             }
-            for (int gi = 0; gi < o_.geom_iterations; ++gi) run_pass(true, false, false, gi > 0);
+            for (int gi = 0; gi < o_.geom_iterations; ++gi) run_pass(Pass::geometric(gi > 0));
             max_down_--;
         }
         {
@@ -431,9 +445,53 @@ class Driver {
 
   private:
     struct Task {
-        int v;  // problem index
-        bool geom, planar, hier, multi;
+        int view;  // problem index
+        Pass pass;
     };
+
+    void read_problems() {
+        problems_.resize(4096);
+        int n = 0;
+        acmmp_check(acmmp_generate_sample_list(o_.dense.c_str(), problems_.data(), (int)problems_.size(), &n),
+                    "GenerateSampleList");
+        problems_.resize((size_t)n);
+        acmmp_check(acmmp_compute_multiscale_settings(o_.dense.c_str(), problems_.data(), n, &max_down_),
+                    "ComputeMultiScaleSettings");
+        for (int i = 0; i < n; ++i) index_of_[problems_[(size_t)i].ref_image_id] = i;
+        state_.resize((size_t)n);
+    }
+
+    // LPT on W*H*max(N-1, 1) of the full-size reference image
+    void plan() {
+        std::vector<double> cost;
+        for (const acmmp_problem &p : problems_) {
+            int w = 0, h = 0;
+            acmmp_check(acmmp_view_size(o_.dense.c_str(), p.ref_image_id, 0, &w, &h), "image header");
+            cost.push_back((double)w * h * std::max(p.num_src_images, 1));
+        }
+        plan_ = plan_views(cost, g_.world, o_.split_tail);
+    }
+
+    // two engines per GPU by default, each with a stream for the driver's own copies
+    void create_engines() {
+        for (int k = 0; k < std::max(o_.concurrent_views, 1); ++k) {
+            acmmp_ctx *ctx = nullptr;
+            acmmp_check(acmmp_create(o_.device, &ctx), "acmmp_create");
+            engines_.push_back(ctx);
+            hipStream_t cs = nullptr;
+            hip_check(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking), "hipStreamCreate");
+            copy_.push_back(cs);
+        }
+    }
+
+    const std::vector<int> &owned() const { return plan_.owned(g_.rank); }
+    // the views this rank computes: its own whole, then a band of every split one
+    std::vector<int> computed() const {
+        std::vector<int> views = plan_.mine(g_.rank);
+        views.insert(views.end(), plan_.split.begin(), plan_.split.end());
+        return views;
+    }
+    const acmmp_camera &ref_cam(int v) const { return cams_.at(problems_[(size_t)v].ref_image_id); }
 
     // wall seconds per phase (ACMMP_HOST_TIMING=1 prints them)
     struct Clock {
@@ -458,14 +516,14 @@ class Driver {
 
     // a pass's outputs written by 4 host threads while the next pass computes
     void start_writes(bool geom) {
-        const int nw = (int)std::min<size_t>(4, owned_.size());
+        const int nw = (int)std::min<size_t>(4, owned().size());
         write_errs_.assign((size_t)nw, std::string());
         for (int w = 0; w < nw; ++w)
             writers_.emplace_back([this, w, nw, geom]() {
                 try {
                     hip_check(hipSetDevice(o_.device), "hipSetDevice");
-                    for (size_t k = (size_t)w; k < owned_.size(); k += (size_t)nw)
-                        write_outputs(owned_[k], state_.at(owned_[k]), geom);
+                    for (size_t k = (size_t)w; k < owned().size(); k += (size_t)nw)
+                        write_outputs(owned()[k], state_[(size_t)owned()[k]], geom);
                 } catch (const std::exception &e) {
                     write_errs_[(size_t)w] = e.what();
                 }
@@ -482,10 +540,9 @@ class Driver {
         textures_.clear();
         images_.clear();
         cams_.clear();
+        const std::vector<int> &own = owned();
         std::vector<int> need;
-        std::vector<int> compute_views = mine_;
-        compute_views.insert(compute_views.end(), split_.begin(), split_.end());
-        for (int v : compute_views) {
+        for (int v : computed()) {
             const acmmp_problem &p = problems_[(size_t)v];
             need.push_back(p.ref_image_id);
             for (int s = 0; s < p.num_src_images; ++s) need.push_back(p.src_image_ids[s]);
@@ -496,11 +553,11 @@ class Driver {
             if (!index_of_.count(id)) fail("source id " + std::to_string(id) + " is not a problem index");
         // work items: the cameras of every needed image, the pixels of my refs
         std::vector<acmmp_camera> cams(need.size());
-        std::vector<std::vector<float>> host(owned_.size());
-        std::vector<acmmp_camera> own_cams(owned_.size());
-        const size_t nwork = need.size() + owned_.size();
+        std::vector<std::vector<float>> host(own.size());
+        std::vector<acmmp_camera> own_cams(own.size());
+        const size_t nwork = need.size() + own.size();
         auto image_id = [&](size_t k) {
-            return k < need.size() ? need[k] : problems_[(size_t)owned_[k - need.size()]].ref_image_id;
+            return k < need.size() ? need[k] : problems_[(size_t)own[k - need.size()]].ref_image_id;
         };
         std::string err;
         const int load_rc = parallel_index(
@@ -524,114 +581,80 @@ class Driver {
             err);
         if (load_rc) fail(err);
         // my refs: kept contiguous for JBU, and padded into my all-gather slots
-        DevBuf send((size_t)slots_ * hmax_ * wmax_);
-        hip_check(hipMemset(send.p, 0, send.n * sizeof(float)), "hipMemset");
-        for (size_t k = 0; k < owned_.size(); ++k) {
+        gathered_images_ = PaddedGather(plan_, hmax_, wmax_);
+        for (size_t k = 0; k < own.size(); ++k) {
             const acmmp_camera &c = own_cams[k];
-            const int v = owned_[k];
-            if (c.height != shape_[(size_t)v].first || c.width != shape_[(size_t)v].second)
+            const int v = own[k];
+            if (c.height != height_[(size_t)v] || c.width != width_[(size_t)v])
                 fail("view " + std::to_string(problems_[(size_t)v].ref_image_id) + ": image size disagrees with its header");
             DevBuf d(host[k].size());
             hip_check(hipMemcpy(d.p, host[k].data(), host[k].size() * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy");
-            hip_check(hipMemcpy2D(send.p + k * (size_t)hmax_ * wmax_, (size_t)wmax_ * sizeof(float), d.p,
-                                  (size_t)c.width * sizeof(float), (size_t)c.width * sizeof(float), (size_t)c.height,
-                                  hipMemcpyDeviceToDevice),
-                      "hipMemcpy2D");
+            gathered_images_.put(v, d.p, c.width, c.height);
             images_.emplace(problems_[(size_t)v].ref_image_id, std::move(d));
         }
-        hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
-        recv_img_ = DevBuf(send.n * (size_t)g_.world);
-        ex_.allgather(send.p, recv_img_.p, send.n);
+        gathered_images_.gather(ex_);
+        gathered_images_.drop_send();
         // the padded footprint records, built once per image and scale from
         // the gathered image (row pitch Wmax)
         for (size_t k = 0; k < need.size(); ++k) {
             const acmmp_camera &c = cams[k];
-            const float *img = gathered_in(recv_img_, index_of_.at(need[k]));
             acmmp_texture *t = nullptr;
-            acmmp_check(acmmp_texture_create(o_.device, img, wmax_, c.width, c.height, &t), "acmmp_texture_create");
+            acmmp_check(acmmp_texture_create(o_.device, gathered_images_.map(index_of_.at(need[k])),
+                                             gathered_images_.pitch(), c.width, c.height, &t),
+                        "acmmp_texture_create");
             textures_[need[k]] = t;
             cams_[need[k]] = c;
         }
         // a split view's JBU runs on every rank: its reference image, unpadded
-        for (int v : split_) {
+        for (int v : plan_.split) {
             const int id = problems_[(size_t)v].ref_image_id;
             if (images_.count(id)) continue;
             const acmmp_camera &c = cams_.at(id);
             DevBuf d((size_t)c.width * c.height);
-            hip_check(hipMemcpy2DAsync(d.p, (size_t)c.width * sizeof(float), gathered_in(recv_img_, v),
-                                       (size_t)wmax_ * sizeof(float), (size_t)c.width * sizeof(float),
-                                       (size_t)c.height, hipMemcpyDeviceToDevice, copy_[0]),
+            hip_check(hipMemcpy2DAsync(d.p, (size_t)c.width * sizeof(float), gathered_images_.map(v),
+                                       (size_t)gathered_images_.pitch() * sizeof(float),
+                                       (size_t)c.width * sizeof(float), (size_t)c.height, hipMemcpyDeviceToDevice,
+                                       copy_[0]),
                       "hipMemcpy2DAsync");
             hip_check(hipStreamSynchronize(copy_[0]), "hipStreamSynchronize");
             images_.emplace(id, std::move(d));
         }
     }
 
-    // (h, w) of every view at this scale
-    void shapes() {
-        shape_.assign(problems_.size(), {0, 0});
-        int hmax = 0, wmax = 0;
+    // height and width of every view at this scale
+    void read_shapes() {
+        height_.assign(problems_.size(), 0);
+        width_.assign(problems_.size(), 0);
+        hmax_ = wmax_ = 0;
         for (size_t i = 0; i < problems_.size(); ++i) {
-            int w = 0, h = 0;
-            acmmp_check(acmmp_view_size(o_.dense.c_str(), problems_[i].ref_image_id, problems_[i].cur_image_size, &w, &h),
+            acmmp_check(acmmp_view_size(o_.dense.c_str(), problems_[i].ref_image_id, problems_[i].cur_image_size,
+                                        &width_[i], &height_[i]),
                         "image header");
-            shape_[i] = {h, w};
-            hmax = std::max(hmax, h);
-            wmax = std::max(wmax, w);
+            hmax_ = std::max(hmax_, height_[i]);
+            wmax_ = std::max(wmax_, width_[i]);
         }
-        if (!split_checked_) {  // every band must hold the halo at the coarsest scale (this one)
-            split_checked_ = true;
-            std::vector<int> keep;
-            for (int v : split_) {
-                if (shape_[(size_t)v].first >= g_.world * ACMMP_BAND_HALO) {
-                    keep.push_back(v);
-                } else if (std::find(owned_.begin(), owned_.end(), v) != owned_.end()) {
-                    mine_.push_back(v);  // its owner computes it whole
-                    std::sort(mine_.begin(), mine_.end());
-                }
-            }
-            split_ = keep;
-        }
-        slots_ = 1;
-        for (auto &a : assignment_) slots_ = std::max(slots_, (int)a.size());
-        hmax_ = hmax;
-        wmax_ = wmax;
-        const size_t per = (size_t)slots_ * hmax_ * wmax_;
-        send_ = DevBuf(per);
-        recv_ = DevBuf(per * (size_t)g_.world);
-        depth_tmp_.clear();
     }
 
-    acmmp_params view_params(const Task &t) const {
+    acmmp_params view_params(int v, const Pass &pass) const {
         acmmp_params p;
         acmmp_default_params(&p);
-        if (t.geom) {  // SetGeomConsistencyParams (src/ACMMP.cpp:447-454)
+        if (pass.geom) {  // SetGeomConsistencyParams (src/ACMMP.cpp:447-454)
             p.geom_consistency = 1;
             p.max_iterations = 2;
-            if (t.multi) p.multi_geometry = 1;
+            if (pass.multi) p.multi_geometry = 1;
         }
-        if (t.hier) p.hierarchy = 1;
-        const acmmp_problem &pr = problems_[(size_t)t.v];
-        p.seed_lo = o_.seed + (unsigned)pr.ref_image_id;
+        if (pass.hier) p.hierarchy = 1;
+        p.seed_lo = o_.seed + (unsigned)problems_[(size_t)v].ref_image_id;
         p.seed_hi = (unsigned)pass_index_;
         if (o_.iterations > 0) p.max_iterations = o_.iterations;
         return p;
     }
 
-    // problem i's map in a padded all-gather buffer (row pitch Wmax)
-    const float *gathered_in(const DevBuf &buf, int i) const {
-        for (int r = 0; r < g_.world; ++r) {
-            const auto &a = assignment_[(size_t)r];
-            for (size_t k = 0; k < a.size(); ++k)
-                if (a[k] == i) return buf.p + ((size_t)r * slots_ + k) * hmax_ * wmax_;
-        }
-        fail("view not assigned");
-    }
-    // the gathered depth map of problem i (previous pass)
-    const float *gathered(int i) const { return gathered_in(recv_, i); }
-
-    void compute(acmmp_ctx *eng, const Task &t, ViewState &out, hipStream_t cs, bool band = false) {
-        const acmmp_problem &pr = problems_[(size_t)t.v];
+    // One view's inputs on an engine: parameters and textures, and for a
+    // geometric pass the gathered depth maps of the previous pass (borrowed in
+    // place) and the view's previous state.
+    void set_view_inputs(acmmp_ctx *eng, const Task &t) {
+        const acmmp_problem &pr = problems_[(size_t)t.view];
         std::vector<int> ids = {pr.ref_image_id};
         for (int s = 0; s < pr.num_src_images; ++s) ids.push_back(pr.src_image_ids[s]);
         std::vector<acmmp_camera> cams;
@@ -640,74 +663,72 @@ class Driver {
             cams.push_back(cams_.at(id));
             tex.push_back(textures_.at(id));
         }
-        const acmmp_params p = view_params(t);
+        const acmmp_params p = view_params(t.view, t.pass);
         acmmp_check(acmmp_set_params(eng, &p), "acmmp_set_params", eng);
         acmmp_check(acmmp_set_images_textures(eng, (int)ids.size(), cams.data(), tex.data(), 0),
                     "acmmp_set_images_textures", eng);
-        const int W = cams[0].width, H = cams[0].height;
-        ViewState &prev = state_[t.v];
-        if (t.geom) {
-            std::vector<const float *> deps;
-            std::vector<int32_t> pitches;
-            for (int id : ids) {
-                deps.push_back(gathered(index_of_.at(id)));
-                pitches.push_back(wmax_);
-            }
-            acmmp_check(acmmp_set_depth_maps_device(eng, deps.data(), pitches.data()), "acmmp_set_depth_maps_device",
-                        eng);
-            acmmp_check(acmmp_set_plane_hypotheses_device(eng, prev.planes.p, prev.costs.p),
-                        "acmmp_set_plane_hypotheses_device", eng);
-        }
-        DevBuf scaled;  // alive until the run below has been synchronised
-        if (t.hier) {  // scaled planes = previous scale's normals + (costs, or the JBU depth when no upsample)
-            const int sh = prev.H, sw = prev.W;
-            const size_t S = (size_t)sh * sw;
-            const bool upsample = sw != H || sh != W;  // src/ACMMP.cpp:766, rows/cols swap included
-            if (!upsample && prev.jbu.n < S) fail("hierarchy input: JBU depth smaller than the scaled planes");
-            scaled = DevBuf(S * 4);
-            // built on the device: the normals, then the 4th channel as a
-            // strided copy (4 of every 16 bytes), as the Python driver does
-            // (device-to-device hipMemcpy does not wait for the copy, and the
-            // engine stream is non-blocking: copy on `cs` and wait for it)
-            hip_check(hipMemcpyAsync(scaled.p, prev.planes.p, S * 4 * sizeof(float), hipMemcpyDeviceToDevice, cs),
-                      "hipMemcpyAsync");
-            hip_check(hipMemcpy2DAsync(scaled.p + 3, 4 * sizeof(float), upsample ? prev.costs.p : prev.jbu.p,
-                                       sizeof(float), sizeof(float), S, hipMemcpyDeviceToDevice, cs),
-                      "hipMemcpy2DAsync");
-            hip_check(hipStreamSynchronize(cs), "hipStreamSynchronize");
-            acmmp_check(acmmp_set_hierarchy_inputs_device(eng, scaled.p, sw, sh, prev.jbu.p),
-                        "acmmp_set_hierarchy_inputs_device", eng);
-        }
-        out.W = W;
-        out.H = H;
-        out.planes = DevBuf((size_t)W * H * 4);
-        out.costs = DevBuf((size_t)W * H);
-        DevBuf depth((size_t)W * H);
-        if (band) {
-            run_band(eng, t, out, depth, cs);
-        } else {
-            acmmp_check(acmmp_run_patchmatch_async(eng), "acmmp_run_patchmatch_async", eng);
-            if (t.planar) {
-                acmmp_check(acmmp_synchronize(eng), "acmmp_synchronize", eng);
-                int nsp = 0, ntri = 0;
-                acmmp_check(acmmp_prepare_planar_prior(eng, &nsp, &ntri), "acmmp_prepare_planar_prior", eng);
-                acmmp_check(acmmp_run_patchmatch_async(eng), "acmmp_run_patchmatch_async", eng);
-            }
-            acmmp_check(acmmp_export_results(eng, out.planes.p, out.costs.p, depth.p), "acmmp_export_results", eng);
+        if (!t.pass.geom) return;
+        std::vector<const float *> deps;
+        for (int id : ids) deps.push_back(depths_.map(index_of_.at(id)));
+        const std::vector<int32_t> pitches(ids.size(), depths_.pitch());
+        acmmp_check(acmmp_set_depth_maps_device(eng, deps.data(), pitches.data()), "acmmp_set_depth_maps_device", eng);
+        const ViewState &prev = state_[(size_t)t.view];
+        acmmp_check(acmmp_set_plane_hypotheses_device(eng, prev.planes.p, prev.costs.p),
+                    "acmmp_set_plane_hypotheses_device", eng);
+    }
+
+    // The hierarchy pass's inputs of a W x H view from its previous scale:
+    // scaled planes = that scale's normals + (costs, or the JBU depth when no
+    // upsample). The engine borrows the returned buffer until its run has
+    // been synchronised.
+    DevBuf set_hierarchy_inputs(acmmp_ctx *eng, const ViewState &prev, int W, int H, hipStream_t cs) {
+        const int sh = prev.H, sw = prev.W;
+        const size_t S = (size_t)sh * sw;
+        const bool upsample = sw != H || sh != W;  // src/ACMMP.cpp:766, rows/cols swap included
+        if (!upsample && prev.jbu.n < S) fail("hierarchy input: JBU depth smaller than the scaled planes");
+        DevBuf scaled(S * 4);
+        // built on the device: the normals, then the 4th channel as a
+        // strided copy (4 of every 16 bytes), as the Python driver does
+        // (device-to-device hipMemcpy does not wait for the copy, and the
+        // engine stream is non-blocking: copy on `cs` and wait for it)
+        hip_check(hipMemcpyAsync(scaled.p, prev.planes.p, S * 4 * sizeof(float), hipMemcpyDeviceToDevice, cs),
+                  "hipMemcpyAsync");
+        hip_check(hipMemcpy2DAsync(scaled.p + 3, 4 * sizeof(float), upsample ? prev.costs.p : prev.jbu.p,
+                                   sizeof(float), sizeof(float), S, hipMemcpyDeviceToDevice, cs),
+                  "hipMemcpy2DAsync");
+        hip_check(hipStreamSynchronize(cs), "hipStreamSynchronize");
+        acmmp_check(acmmp_set_hierarchy_inputs_device(eng, scaled.p, sw, sh, prev.jbu.p),
+                    "acmmp_set_hierarchy_inputs_device", eng);
+        return scaled;
+    }
+
+    // One view of a pass on an engine, by `run` (run_whole, or run_band on
+    // every rank at once): its inputs, then its new state.
+    using Run = void (Driver::*)(acmmp_ctx *, const Pass &, ViewState &, hipStream_t);
+    ViewState compute(acmmp_ctx *eng, const Task &t, hipStream_t cs, Run run) {
+        set_view_inputs(eng, t);
+        const acmmp_camera &c = ref_cam(t.view);
+        DevBuf scaled;
+        if (t.pass.hier) scaled = set_hierarchy_inputs(eng, state_[(size_t)t.view], c.width, c.height, cs);
+        ViewState out(c.width, c.height);
+        (this->*run)(eng, t.pass, out, cs);
+        return out;
+    }
+
+    // RunPatchMatch, twice with the planar prior between (src/acmmp_definitions.cpp:306-379)
+    void run_whole(acmmp_ctx *eng, const Pass &pass, ViewState &out, hipStream_t) {
+        acmmp_check(acmmp_run_patchmatch_async(eng), "acmmp_run_patchmatch_async", eng);
+        if (pass.planar) {
             acmmp_check(acmmp_synchronize(eng), "acmmp_synchronize", eng);
+            int nsp = 0, ntri = 0;
+            acmmp_check(acmmp_prepare_planar_prior(eng, &nsp, &ntri), "acmmp_prepare_planar_prior", eng);
+            acmmp_check(acmmp_run_patchmatch_async(eng), "acmmp_run_patchmatch_async", eng);
         }
-        std::lock_guard<std::mutex> lk(mu_);
-        depth_tmp_[t.v] = std::move(depth);
+        acmmp_check(acmmp_export_results(eng, out.planes.p, out.costs.p, out.depth.p), "acmmp_export_results", eng);
+        acmmp_check(acmmp_synchronize(eng), "acmmp_synchronize", eng);
     }
 
-    bool is_split(int v) const { return std::find(split_.begin(), split_.end(), v) != split_.end(); }
-
-    // rows [lo, hi) of band k of H rows over the world (sizes differ by at most 1)
-    std::pair<int, int> band_rows(int H, int k) const {
-        const int base = H / g_.world, extra = H % g_.world;
-        const int lo = k * base + std::min(k, extra);
-        return {lo, lo + base + (k < extra ? 1 : 0)};
-    }
+    std::pair<int, int> band_rows(int H, int k) const { return acmmp_vp::band_rows(H, g_.world, k); }
 
     // The halo exchange of a band run (acmmp_run_patchmatch_band's callback):
     // each rank all-gathers [rows the band above reads | rows the band below
@@ -739,33 +760,19 @@ class Driver {
         }
         // the sweep that wrote these rows ran on the engine's stream
         hip_check(hipStreamSynchronize((hipStream_t)h.stream), "hipStreamSynchronize");
-        auto pack = [&](float *dst, int lo, int hi) {
-            const size_t n = (size_t)(hi - lo) * Wh;
-            if (!n) return;
-            hip_check(hipMemcpyAsync(dst, (const float *)h.plane + (size_t)lo * Wh * 4, n * 16, hipMemcpyDeviceToDevice,
-                                     b.cs), "hipMemcpyAsync");
-            hip_check(hipMemcpyAsync(dst + K * Wh * 4, (const float *)h.cost + (size_t)lo * Wh, n * 4,
-                                     hipMemcpyDeviceToDevice, b.cs), "hipMemcpyAsync");
-            hip_check(hipMemcpyAsync(dst + K * Wh * 5, (const uint32_t *)h.sv + (size_t)lo * Wh, n * 4,
-                                     hipMemcpyDeviceToDevice, b.cs), "hipMemcpyAsync");
+        // rows [lo, hi) of the three maps, to (pack) or from one part
+        auto rows = [&](float *p, int lo, int hi, bool pack) {
+            copy_rows(h.plane, Wh * 4, lo, hi, p, pack, b.cs);
+            copy_rows(h.cost, Wh, lo, hi, p + K * Wh * 4, pack, b.cs);
+            copy_rows(h.sv, Wh, lo, hi, p + K * Wh * 5, pack, b.cs);
         };
-        auto unpack = [&](const float *src, int lo, int hi) {
-            const size_t n = (size_t)(hi - lo) * Wh;
-            if (!n) return;
-            hip_check(hipMemcpyAsync((float *)h.plane + (size_t)lo * Wh * 4, src, n * 16, hipMemcpyDeviceToDevice, b.cs),
-                      "hipMemcpyAsync");
-            hip_check(hipMemcpyAsync((float *)h.cost + (size_t)lo * Wh, src + K * Wh * 4, n * 4,
-                                     hipMemcpyDeviceToDevice, b.cs), "hipMemcpyAsync");
-            hip_check(hipMemcpyAsync((uint32_t *)h.sv + (size_t)lo * Wh, src + K * Wh * 5, n * 4,
-                                     hipMemcpyDeviceToDevice, b.cs), "hipMemcpyAsync");
-        };
-        pack(b.send.p, h.send_up_lo, h.send_up_hi);
-        pack(b.send.p + part, h.send_down_lo, h.send_down_hi);
+        rows(b.send.p, h.send_up_lo, h.send_up_hi, true);
+        rows(b.send.p + part, h.send_down_lo, h.send_down_hi, true);
         hip_check(hipStreamSynchronize(b.cs), "hipStreamSynchronize");
         ex_.allgather(b.send.p, b.recv.p, b.send.n);
         const int r = g_.rank;
-        if (r > 0) unpack(b.recv.p + (size_t)(r - 1) * 2 * part + part, h.recv_up_lo, h.recv_up_hi);
-        if (r + 1 < g_.world) unpack(b.recv.p + (size_t)(r + 1) * 2 * part, h.recv_down_lo, h.recv_down_hi);
+        if (r > 0) rows(b.recv.p + (size_t)(r - 1) * 2 * part + part, h.recv_up_lo, h.recv_up_hi, false);
+        if (r + 1 < g_.world) rows(b.recv.p + (size_t)(r + 1) * 2 * part, h.recv_down_lo, h.recv_down_hi, false);
         // the engine's next sweep is enqueued after this returns
         hip_check(hipStreamSynchronize(b.cs), "hipStreamSynchronize");
     }
@@ -777,22 +784,25 @@ class Driver {
         for (int k = 0; k < g_.world; ++k) rmax = std::max(rmax, band_rows(H, k).second - band_rows(H, k).first);
         const size_t per = (size_t)rmax * W * 5;
         DevBuf send(per), recv(per * (size_t)g_.world);
-        const auto [lo, hi] = band_rows(H, g_.rank);
-        hip_check(hipMemcpyAsync(send.p, out.planes.p + (size_t)lo * W * 4, (size_t)(hi - lo) * W * 16,
-                                 hipMemcpyDeviceToDevice, cs), "hipMemcpyAsync");
-        hip_check(hipMemcpyAsync(send.p + (size_t)rmax * W * 4, out.costs.p + (size_t)lo * W, (size_t)(hi - lo) * W * 4,
-                                 hipMemcpyDeviceToDevice, cs), "hipMemcpyAsync");
+        // band k's rows of both maps, to (pack) or from its rank's block
+        auto band = [&](int k, float *block, bool pack) {
+            const auto [lo, hi] = band_rows(H, k);
+            copy_rows(out.planes.p, (size_t)W * 4, lo, hi, block, pack, cs);
+            copy_rows(out.costs.p, (size_t)W, lo, hi, block + (size_t)rmax * W * 4, pack, cs);
+        };
+        band(g_.rank, send.p, true);
         hip_check(hipStreamSynchronize(cs), "hipStreamSynchronize");
         ex_.allgather(send.p, recv.p, per);
-        for (int k = 0; k < g_.world; ++k) {
-            if (k == g_.rank) continue;
-            const auto [blo, bhi] = band_rows(H, k);
-            const float *src = recv.p + (size_t)k * per;
-            hip_check(hipMemcpyAsync(out.planes.p + (size_t)blo * W * 4, src, (size_t)(bhi - blo) * W * 16,
-                                     hipMemcpyDeviceToDevice, cs), "hipMemcpyAsync");
-            hip_check(hipMemcpyAsync(out.costs.p + (size_t)blo * W, src + (size_t)rmax * W * 4,
-                                     (size_t)(bhi - blo) * W * 4, hipMemcpyDeviceToDevice, cs), "hipMemcpyAsync");
-        }
+        for (int k = 0; k < g_.world; ++k)
+            if (k != g_.rank) band(k, recv.p + (size_t)k * per, false);
+        hip_check(hipStreamSynchronize(cs), "hipStreamSynchronize");
+    }
+
+    // the depth channel of the gathered planes (a band export has no whole depth map)
+    void extract_depth(ViewState &s, hipStream_t cs) {
+        hip_check(hipMemcpy2DAsync(s.depth.p, sizeof(float), s.planes.p + 3, 4 * sizeof(float), sizeof(float),
+                                   (size_t)s.W * s.H, hipMemcpyDeviceToDevice, cs),
+                  "hipMemcpy2DAsync");
         hip_check(hipStreamSynchronize(cs), "hipStreamSynchronize");
     }
 
@@ -800,11 +810,11 @@ class Driver {
     // holds the view's inputs): this rank's band, the halos exchanged every
     // half-sweep, the bands gathered; with the planar prior, the prior is
     // rebuilt on every rank from the gathered first run, then the second run
-    // (src/acmmp_definitions.cpp:306-379). `depth` = the planes' w channel.
-    void run_band(acmmp_ctx *eng, const Task &t, ViewState &out, DevBuf &depth, hipStream_t cs) {
+    // (src/acmmp_definitions.cpp:306-379).
+    void run_band(acmmp_ctx *eng, const Pass &pass, ViewState &out, hipStream_t cs) {
         const auto [lo, hi] = band_rows(out.H, g_.rank);
         BandCtx b{this, cs, {}, {}, {}};
-        for (int run = 0; run < (t.planar ? 2 : 1); ++run) {
+        for (int run = 0; run < (pass.planar ? 2 : 1); ++run) {
             if (run) {
                 acmmp_check(acmmp_set_plane_hypotheses_device(eng, out.planes.p, out.costs.p),
                             "acmmp_set_plane_hypotheses_device", eng);
@@ -818,11 +828,7 @@ class Driver {
             acmmp_check(acmmp_synchronize(eng), "acmmp_synchronize", eng);
             gather_bands(out, cs);
         }
-        const size_t P = (size_t)out.W * out.H;
-        hip_check(hipMemcpy2DAsync(depth.p, sizeof(float), out.planes.p + 3, 4 * sizeof(float), sizeof(float), P,
-                                   hipMemcpyDeviceToDevice, cs),
-                  "hipMemcpy2DAsync");
-        hip_check(hipStreamSynchronize(cs), "hipStreamSynchronize");
+        extract_depth(out, cs);
     }
 
     void write_outputs(int v, const ViewState &s, bool geom) {
@@ -836,25 +842,18 @@ class Driver {
             fail("cannot write the .dmb outputs of view " + std::to_string(problems_[(size_t)v].ref_image_id));
     }
 
-    void run_pass(bool geom, bool planar, bool hier, bool multi) {
+    void run_pass(const Pass &pass) {
         std::vector<Task> tasks;
-        for (int v : mine_) tasks.push_back({v, geom, planar, hier, multi});
-        std::map<int, ViewState> next;
-        for (int v : mine_) {  // every key exists before the worker threads look them up
-            next[v];
-            state_[v];
-        }
-        for (int v : split_) {
-            next[v];
-            state_[v];
-        }
+        for (int v : plan_.mine(g_.rank)) tasks.push_back({v, pass});
+        std::vector<ViewState> next(state_.size());
         // views off a shared queue, one host thread per engine
         std::atomic<size_t> q{0};
         std::vector<std::string> errs(engines_.size());
         auto worker = [&](size_t e) {
             try {
                 hip_check(hipSetDevice(o_.device), "hipSetDevice");  // per thread: the output buffers go there
-                for (size_t k; (k = q++) < tasks.size();) compute(engines_[e], tasks[k], next[tasks[k].v], copy_[e]);
+                for (size_t k; (k = q++) < tasks.size();)
+                    next[(size_t)tasks[k].view] = compute(engines_[e], tasks[k], copy_[e], &Driver::run_whole);
             } catch (const std::exception &ex) {
                 errs[e] = ex.what();
                 q = tasks.size();
@@ -868,56 +867,41 @@ class Driver {
         }
         for (auto &e : errs)
             if (!e.empty()) fail(e);
-        if (!split_.empty()) {  // the tail views, every rank on a band of each
+        if (!plan_.split.empty()) {  // the tail views, every rank on a band of each
             Clock c(this, "split_compute");
-            for (int v : split_) compute(engines_[0], Task{v, geom, planar, hier, multi}, next[v], copy_[0], true);
+            for (int v : plan_.split)
+                next[(size_t)v] = compute(engines_[0], Task{v, pass}, copy_[0], &Driver::run_band);
         }
         {
             Clock c(this, "flush_writes");
             flush_writes();  // the previous pass's writers still read the state replaced below
         }
         Clock c(this, "exchange");
-        // state, then the padded all-gather of the depth maps; the outputs are
-        // written while the next pass computes
-        hip_check(hipMemset(send_.p, 0, send_.n * sizeof(float)), "hipMemset");
-        for (int v : split_)  // every rank holds the split views' full state
-            if (std::find(owned_.begin(), owned_.end(), v) == owned_.end()) state_[v] = std::move(next[v]);
-        for (size_t k = 0; k < owned_.size(); ++k) {
-            const int v = owned_[k];
-            ViewState &s = next[v];
-            hip_check(hipMemcpy2D(send_.p + k * (size_t)hmax_ * wmax_, (size_t)wmax_ * sizeof(float),
-                                  depth_tmp_.at(v).p, (size_t)s.W * sizeof(float), (size_t)s.W * sizeof(float),
-                                  (size_t)s.H, hipMemcpyDeviceToDevice),
-                      "hipMemcpy2D");
-            state_[v] = std::move(s);
+        // state (every rank holds the split views' full state), then the padded
+        // all-gather of the depth maps; the outputs are written while the
+        // all-gather waits for the other ranks and the next pass computes
+        for (int v : computed()) state_[(size_t)v] = std::move(next[(size_t)v]);
+        for (int v : owned()) {
+            const ViewState &s = state_[(size_t)v];
+            depths_.put(v, s.depth.p, s.W, s.H);
         }
-        hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
-        depth_tmp_.clear();
-        if (o_.write_outputs) start_writes(geom);
-        ex_.allgather(send_.p, recv_.p, send_.n);
+        if (o_.write_outputs) start_writes(pass.geom);
+        depths_.gather(ex_);
         pass_index_++;
     }
 
-    // JointBilateralUpsampling of each owned view's previous-scale depth to
-    // this scale's image (src/ACMMP.cpp:964-1087) on the device, kept there
-    // for the hierarchy pass
+    // JointBilateralUpsampling of each computed view's previous-scale depth
+    // to this scale's image (src/ACMMP.cpp:964-1087) on the device, kept
+    // there for the hierarchy pass
     void jbu() {
-        std::vector<int> views = mine_;
-        views.insert(views.end(), split_.begin(), split_.end());
-        for (int v : views) {
-            ViewState &s = state_[v];
+        for (int v : computed()) {
+            ViewState &s = state_[(size_t)v];
             const int id = problems_[(size_t)v].ref_image_id;
             const acmmp_camera &c = cams_.at(id);
-            const size_t P = (size_t)s.W * s.H;
-            DevBuf d(P);  // the depth channel of the previous scale's planes
-            hip_check(hipMemcpy2DAsync(d.p, sizeof(float), s.planes.p + 3, 4 * sizeof(float), sizeof(float), P,
-                                       hipMemcpyDeviceToDevice, copy_[0]),
-                      "hipMemcpy2DAsync");
-            hip_check(hipStreamSynchronize(copy_[0]), "hipStreamSynchronize");  // the JBU runs on its own stream
             s.jbu = DevBuf((size_t)c.width * c.height);
             int isc = 0;
-            acmmp_check(acmmp_joint_bilateral_upsample_device(o_.device, images_.at(id).p, c.width, c.height, d.p, s.W,
-                                                              s.H, s.jbu.p, &isc),
+            acmmp_check(acmmp_joint_bilateral_upsample_device(o_.device, images_.at(id).p, c.width, c.height,
+                                                              s.depth.p, s.W, s.H, s.jbu.p, &isc),
                         "acmmp_joint_bilateral_upsample_device");
             if (isc <= 1) fail("view " + std::to_string(id) + ": JBU image scale 1 (nothing to upsample)");
         }
@@ -930,23 +914,17 @@ class Driver {
     std::vector<acmmp_problem> problems_;
     std::map<int, int> index_of_;
     int max_down_ = -1;
-    std::vector<std::vector<int>> assignment_;
-    std::vector<int> mine_;   // views this rank computes whole
-    std::vector<int> owned_;  // views whose image / depth slot and .dmb files are this rank's
-    std::vector<int> split_;  // views every rank computes a band of
-    bool split_checked_ = false;
+    Plan plan_;  // who owns, computes and splits which view; the all-gather slots
     std::vector<acmmp_ctx *> engines_;
     std::vector<hipStream_t> copy_;  // per engine: the driver's device-to-device copies
     std::map<int, DevBuf> images_;
     std::map<int, acmmp_texture *> textures_;  // ~ the reference's texture objects, per image and scale
     std::map<int, acmmp_camera> cams_;
-    std::vector<std::pair<int, int>> shape_;
-    int slots_ = 1, hmax_ = 0, wmax_ = 0;
-    DevBuf send_, recv_;
-    DevBuf recv_img_;  // this scale's images of every view, gathered (textures borrow it)
-    std::map<int, DevBuf> depth_tmp_;
-    std::map<int, ViewState> state_;
-    std::mutex mu_;
+    std::vector<int> height_, width_;  // of every view at this scale
+    int hmax_ = 0, wmax_ = 0;
+    PaddedGather gathered_images_;  // this scale's images of every view (textures borrow it)
+    PaddedGather depths_;           // the previous pass's depth maps of every view
+    std::vector<ViewState> state_;  // per problem index: the views this rank computes
     int pass_index_ = 0;
     std::vector<std::thread> writers_;
     std::vector<std::string> write_errs_;

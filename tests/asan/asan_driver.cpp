@@ -17,6 +17,7 @@
 //                      (a fusion folder = RunPriorAwareFusion, - = RunFusion)
 //   asan_driver fusion_fails <same arguments>  the fusion must return an error status
 //   asan_driver oracle <seed>                  CPU oracle RunPatchMatch branches, JBU, planar
+//   asan_driver plan < cases                   the view-parallel driver's plan (acmmp_vp_plan.h), printed
 // Exit 0 = every call returned (any status; fusion: ACMMP_OK, fusion_fails:
 // another status); sanitizer findings abort.
 #include <unistd.h>
@@ -29,6 +30,7 @@
 #include <vector>
 
 #include "../../include/acmmp.h"
+#include "../../acmmp_amd/csrc/acmmp_vp_plan.h"
 
 extern "C" {
 // oracle/acmmp_oracle.c, oracle/acmmp_oracle_planar.c
@@ -339,6 +341,59 @@ int run_oracle() {
     return 0;
 }
 
+void print_list(const std::vector<int> &v) {
+    std::printf("[");
+    for (size_t i = 0; i < v.size(); ++i) std::printf("%s%d", i ? "," : "", v[i]);
+    std::printf("]");
+}
+
+// One case per stdin line, `world split_tail cost:height ...`; one JSON line
+// per case with everything acmmp_vp_plan.h decides (heights = the coarsest
+// scale's; the layout's offsets for maps of max height x 3 floats).
+int run_plan() {
+    char line[4096];
+    while (std::fgets(line, sizeof line, stdin)) {
+        char *s = line;
+        const int world = (int)std::strtol(s, &s, 10);
+        const bool split_tail = std::strtol(s, &s, 10) != 0;
+        std::vector<double> costs;
+        std::vector<int> heights;
+        for (;;) {
+            char *e = s;
+            const double c = std::strtod(s, &e);
+            if (e == s || *e != ':') break;
+            costs.push_back(c);
+            heights.push_back((int)std::strtol(e + 1, &s, 10));
+        }
+        if (world < 1 || costs.empty()) return 2;
+        acmmp_vp::Plan p = acmmp_vp::plan_views(costs, world, split_tail);
+        p.apply_halo_rule(heights);
+        int hmax = 0;
+        for (int h : heights) hmax = std::max(hmax, h);
+        const acmmp_vp::GatherLayout at{&p, hmax, 3};
+        std::printf("{\"assignment\":[");
+        for (int r = 0; r < world; ++r) std::printf("%s", r ? "," : ""), print_list(p.owned(r));
+        std::printf("],\"split\":"), print_list(p.split);
+        std::printf(",\"mine\":[");
+        for (int r = 0; r < world; ++r) std::printf("%s", r ? "," : ""), print_list(p.mine(r));
+        std::printf("],\"slots\":%d,\"slot\":", p.slots), print_list(p.slot);
+        std::printf(",\"floats\":[%zu,%zu],\"offsets\":[", at.send_floats(), at.recv_floats());
+        for (size_t v = 0; v < costs.size(); ++v)
+            std::printf("%s[%zu,%zu]", v ? "," : "", at.send_offset((int)v), at.recv_offset((int)v));
+        std::printf("],\"bands\":{");
+        for (size_t i = 0; i < p.split.size(); ++i) {
+            std::printf("%s\"%d\":[", i ? "," : "", p.split[i]);
+            for (int k = 0; k < world; ++k) {
+                const auto b = acmmp_vp::band_rows(heights[(size_t)p.split[i]], world, k);
+                std::printf("%s[%d,%d]", k ? "," : "", b.first, b.second);
+            }
+            std::printf("]");
+        }
+        std::printf("}}\n");
+    }
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
@@ -366,6 +421,8 @@ int main(int argc, char **argv) {
     } else if (cmd == "oracle") {
         seed_at(2);
         rc = run_oracle();
+    } else if (cmd == "plan") {
+        rc = run_plan();
     }
     if (rc == 0) std::printf("%s ok\n", cmd.c_str());
     return rc;

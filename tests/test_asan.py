@@ -38,8 +38,8 @@ def driver():
     return DRIVER
 
 
-def run(args, cwd, timeout=300):
-    r = subprocess.run(args, cwd=cwd, env=ENV, capture_output=True, text=True, timeout=timeout)
+def run(args, cwd, timeout=300, stdin=None):
+    r = subprocess.run(args, cwd=cwd, env=ENV, capture_output=True, text=True, timeout=timeout, input=stdin)
     out = r.stdout + r.stderr
     assert "ERROR: AddressSanitizer" not in out and "runtime error:" not in out, out[-4000:]
     assert r.returncode == 0, out[-4000:]
@@ -98,6 +98,66 @@ def test_oracle_branches(driver, tmp_path):
     """RunPatchMatch restatement: photometric, geometric, planar prior,
     hierarchy (upsample), the T1 cost vectors and JBU, at an odd size."""
     run([driver, "oracle", "9"], cwd=tmp_path, timeout=600)
+
+
+def _python_plan(world, split_tail, costs, heights):
+    """What acmmp_amd/distributed.py and band.py decide for the case, in the
+    shape `asan_driver plan` prints."""
+    import torch
+    from acmmp_amd import _abi
+    from acmmp_amd.band import bands
+    from acmmp_amd.distributed import DepthExchange, plan_views
+    assignment, split = plan_views(costs, world, split_tail)
+    split = [v for v in split if heights[v] >= world * _abi.BAND_HALO]  # ViewParallelPipeline._check_split
+    ex = DepthExchange(assignment, {v: (h, 3) for v, h in enumerate(heights)}, torch.device("cpu"))
+    per = ex.hmax * ex.wmax
+    slot, offsets = [None] * len(costs), [None] * len(costs)
+    for r, a in enumerate(assignment):  # DepthExchange.gather: send[k], recv[r * slots + k]
+        for k, v in enumerate(a):
+            slot[v] = r * ex.slots + k
+            offsets[v] = [k * per, slot[v] * per]
+    return {"assignment": assignment, "split": split,
+            "mine": [[v for v in a if v not in split] for a in assignment],
+            "slots": ex.slots, "slot": slot, "floats": [ex.slots * per, world * ex.slots * per], "offsets": offsets,
+            "bands": {str(v): [list(b) for b in bands(heights[v], world)] for v in split}}
+
+
+def test_view_plan_matches_python_driver(driver, tmp_path):
+    """The C++ view-parallel driver's placement (acmmp_vp_plan.h: LPT, tail
+    split, halo rule, band rows, all-gather slots) equals the Python
+    driver's on the fixed cases of test_plan_views_split_tail, the edges of
+    each rule and 300 random cases with frequent cost ties."""
+    import json
+    import random
+    cases = [(8, True, [1.0] * 49, [184] * 49), (8, True, [1.0] * 16, [184] * 16), (8, False, [1.0] * 49, [184] * 49),
+             (2, True, [4.0, 1.0, 3.0, 2.0, 5.0], [120] * 5),
+             (4, True, [2.0, 1.0], [120, 120]),            # n < world: both split
+             (3, True, [3.0, 1.0, 2.0, 2.0, 1.0, 3.0], [120] * 6),  # n % world == 0: none split
+             (1, True, [1.0, 2.0, 3.0], [22] * 3),         # world 1
+             (3, False, [1.0, 2.0, 3.0, 4.0], [120] * 4),  # split_tail off
+             (2, True, [2.0, 2.0, 1.0], [120, 120, 45]),   # one row short of two 23-row bands: computed whole
+             (2, True, [2.0, 2.0, 1.0], [120, 120, 46])]   # just enough: split
+    rng = random.Random(7)
+    for _ in range(300):
+        n, world = rng.randint(1, 24), rng.randint(1, 8)
+        cases.append((world, rng.random() < 0.8, [float(rng.choice([1, 2, 3, 4])) for _ in range(n)],
+                      [rng.choice([22, 45, 46, 69, 120, 184]) for _ in range(n)]))
+    text = "".join("%d %d %s\n" % (w, st, " ".join("%g:%d" % ch for ch in zip(c, h))) for w, st, c, h in cases)
+    out = run([driver, "plan"], cwd=tmp_path, stdin=text).splitlines()
+    assert out[-1] == "plan ok" and len(out) == len(cases) + 1
+    got = [json.loads(line) for line in out[:-1]]
+    for case, g in zip(cases, got):
+        assert g == _python_plan(*case), case
+    assert got[4]["split"] == [0, 1] and got[4]["mine"] == [[], [], [], []]
+    assert got[5]["split"] == [] and got[7]["split"] == []
+    assert got[8]["split"] == [] and got[8]["mine"] == got[8]["assignment"]
+    assert got[9]["split"] == [2] and got[9]["bands"] == {"2": [[0, 23], [23, 46]]}
+    # the random cases fall on both sides of the halo rule
+    tail = [len(c) % w if st and w > 1 else 0 for w, st, c, _ in cases]
+    kept = sum(len(g["split"]) > 0 for g in got)
+    dropped = sum(len(g["split"]) < t for g, t in zip(got, tail))
+    print("cases with a view that stays split:", kept, "with one the rule turns whole:", dropped)
+    assert kept >= 20 and dropped >= 20
 
 
 def test_fusion_and_prior_aware_fusion(driver, tmp_path):

@@ -87,6 +87,34 @@ def test_world2_tcp_matches_oracle_jacobi_and_fuses(dense, jacobi_maps, split):
     assert os.path.getsize(os.path.join(dense + out, "ACMMP_model.ply")) > 1000
 
 
+@pytest.fixture(scope="module")
+def mixed_dense(tmp_path_factory):
+    """3 views at 96x72, the third cropped to its top-left 88x64 (intrinsics
+    unchanged): the padded all-gathers hold a view below the slot's size."""
+    d = str(tmp_path_factory.mktemp("cvp_mixed"))
+    sc = scene.make_scene(num_views=3, width=96, height=72)
+    sc.views[2].image = sc.views[2].image[:64, :88]
+    scene.write_dense_folder(sc, d, num_src=2)
+    return d
+
+
+@pytest.fixture(scope="module")
+def mixed_jacobi_maps(mixed_dense):
+    maps = OraclePipeline(mixed_dense).run_single_scale("jacobi")
+    assert [maps[(i, "depths_geom")].shape for i in range(3)] == [(72, 96), (72, 96), (64, 88)]
+    return maps
+
+
+@pytest.mark.parametrize("split", [True, False])
+def test_world2_tcp_views_of_different_sizes_match_oracle_jacobi(mixed_dense, mixed_jacobi_maps, split):
+    """The smaller view is the tail: with the split it runs as two 32-row
+    bands of 88 columns in a 72x96 slot, and either way it is a source of both
+    other views at row pitch 96 and extent 88x64."""
+    out = "/CVPX" if split else "/CVPXw"
+    _launch(mixed_dense, out, 2, "tcp", ["--no_fusion"] + ([] if split else ["--no_split_tail"]))
+    assert _compare(mixed_dense + out, mixed_jacobi_maps) == 3 * 4
+
+
 @pytest.mark.timeout(900)
 def test_world2_tcp_multi_scale_matches_oracle_jacobi(ms4_dense, ms4_oracle_maps):
     """Two scales (1010x760 -> 505x380 first): planar pass, two geometric
