@@ -133,7 +133,9 @@ class PassOptions(C.Structure):
         ("seed_hi", C.c_uint32),
         ("write_triangulation", C.c_int32),
         ("verbose", C.c_int32),
-        ("reserved", C.c_int32 * 5),
+        ("patch_size", C.c_int32),        # 0: the default, 11
+        ("radius_increment", C.c_int32),  # 0: the default, 2
+        ("reserved", C.c_int32 * 3),
     ]
 
 
@@ -225,6 +227,7 @@ SIGNATURES = {
                                         C.POINTER(PassOptions)]),
     "acmmp_joint_bilateral_upsampling": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(Problem), C.c_int, C.c_int]),
     "acmmp_pipeline_last_error": (C.c_char_p, []),
+    "acmmp_patch_geometry_supported": (C.c_int, [C.c_int, C.c_int]),
     "acmmp_run_fusion": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(Problem), C.c_int, C.c_int, C.c_float, C.c_int,
                                    C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_int)]),
     "acmmp_fusion_last_error": (C.c_char_p, []),

@@ -1,9 +1,10 @@
 // acmmp_dev.h — device helpers shared by the MI355X (gfx950, CDNA4) kernels
 // for ACMMP::RunPatchMatch: textures, geometry, RNG, the reference tile, the
-// NCC rows, the geometric cost and the lane maps. Included by
-// acmmp_kernels.hip (the plain kernels, every launcher, the texel-form
-// dispatch) and by acmmp_kernels_tx.hip (the templated PatchMatch kernels,
-// compiled once per texel form).
+// NCC rows, the geometric cost, the lane maps and the 11 / 2 patch policy
+// (FastPatch; the policy of every other geometry is acmmp_general.h).
+// Included by acmmp_kernels.hip (the plain kernels, every launcher, the
+// texel-form dispatch) and by acmmp_kernels_tx.hip (the templated PatchMatch
+// kernels, compiled once per texel form and patch policy).
 //
 // Reference semantics: rlav440/ACMMP src/ACMMP.cu:17-1352 (device code) with the
 // pinned semantics of SURVEY.md Appendix A and the arithmetic pins P1-P4 listed
@@ -36,8 +37,9 @@ namespace acmmp {
 
 #define DEV static __device__ __forceinline__
 
-// Patch geometry fixed by the reference defaults (patch_size 11, increment 2:
-// offsets {-5,-3,-1,1,3,5}^2, src/ACMMP.h:34,37). The engine rejects others.
+// Patch geometry of the fast path, the reference defaults (patch_size 11,
+// increment 2: offsets {-5,-3,-1,1,3,5}^2, src/ACMMP.h:34,37). The engine
+// sends every other geometry to the general kernels (acmmp_general.h).
 constexpr int kTaps = 6;
 
 // The kernel shapes below are the measured winners of the A/B experiments
@@ -672,14 +674,15 @@ DEV void ncc_sums(const SrcImage &im, const float *H, const PixPatch &pp, int px
     ncc_sums_rows<FAST, TX>(im, H, wl, pp.rt, kThreads, px, py, sum_src, sum_ss, sum_rs);
 }
 
+constexpr float kNccCostMax = 2.0f, kNccMinVar = 1e-5f;
+
 // ComputeBilateralNCC (src/ACMMP.cu:360-432) for source view v (1-based,
 // wave-uniform). Reference samples come from the LDS tile, source samples
 // through ncc_sums.
 template <int TX>
-DEV float bilateral_ncc(const KViews &kv, const float *tile, int tb, const PixPatch &pp, int v, int px,
-                        int py, float4 h) {
-    const float cost_max = 2.0f;
-    const float kMinVar = 1e-5f;
+DEV float bilateral_ncc(const KViews &kv, const PixPatch &pp, int v, int px, int py, float4 h) {
+    const float cost_max = kNccCostMax;
+    const float kMinVar = kNccMinVar;
     // var_ref is invariant: when it is below kMinVar (or the centre maps
     // outside the source) every call returns cost_max.
     if (pp.var < kMinVar) return cost_max;
@@ -715,15 +718,14 @@ DEV float bilateral_ncc(const KViews &kv, const float *tile, int tb, const PixPa
 }
 
 // ComputeMultiViewInitialCostandSelectedViews (src/ACMMP.cu:434-471)
-template <int NS, int TX>
-DEV float initial_cost(const KViews &kv, const float *tile, int tb, const PixPatch &pp, int px, int py,
-                       float4 h, uint32_t &sel) {
+template <int NS, typename P>
+DEV float initial_cost(const KViews &kv, const typename P::Pix &pp, int px, int py, float4 h, uint32_t &sel) {
     const int nsrc = kv.nsrc;
     float cv[NS];
     float cs[NS];
     int num_valid = 0;
     for (int i = 0; i < nsrc; ++i) {
-        const float c = bilateral_ncc<TX>(kv, tile, tb, pp, i + 1, px, py, h);
+        const float c = P::ncc(kv, pp, i + 1, px, py, h);
         cv[i] = c;
         cs[i] = c;
         if (c < 2.0f) num_valid++;
@@ -965,6 +967,55 @@ DEV LaneGeom lane_geom_of(int colour, BlockXY b, int tid) {
 
 DEV LaneGeom lane_geom(int colour, BlockXY b) { return lane_geom_of(colour, b, threadIdx.y * kBX + threadIdx.x); }
 
+// ---------------------------------------------------------- patch policies
+// The PatchMatch kernels (init, sweep, refinement, eval; acmmp_kernels_tx.hip)
+// are written once over a patch policy P, which owns everything that depends
+// on the patch geometry:
+//   P::kTileFloats / kWeightSlots / kLutFloats   sizes of the block's LDS arrays
+//   P::Pix                a pixel's handle: LDS addresses + wo (the lane's index
+//                         in the block), mean, var, inv_wsum, which the bodies read
+//   P::stage(...)         stage the block's reference window (caller syncs)
+//   P::lane(...)          the handle of lane `tid` of the block (any lane)
+//   P::invariants(...)    form a pixel's reference invariants
+//   P::ncc(...)           NCC of plane h against source view v
+// FastPatch is the 11 / 2 code of this file; GeneralPatch (acmmp_general.h)
+// takes radius and increment from KViews::prm.
+struct PatchLds {
+    float *tile;  // the reference window
+    WSlot *w;     // per-lane weight slots
+    float *wlut;  // the u8-form weight table
+};
+
+template <int TX>
+struct FastPatch {
+    static constexpr int kTx = TX;
+    static constexpr int kTileFloats = kTileW * kTileH;
+    static constexpr int kWeightSlots = kSlots * kThreads;
+    static constexpr int kLutFloats = (TX & kTxU8) ? kWlutClasses * 256 : 1;
+    typedef PixPatch Pix;
+
+    // lut: take the bilateral weights from the table (the u8 form's init and sweep)
+    static __device__ __forceinline__ void stage(const KViews &kv, const PatchLds &l, BlockXY blk, int colour,
+                                                 bool lut) {
+        load_ref_tile(kv, l.tile, blk.bx * kBX, blk.by * kBY, colour);
+        if (lut) load_wlut(kv, l.wlut);
+    }
+    static __device__ __forceinline__ Pix lane(const PatchLds &l, const LaneGeom &g, BlockXY, int tid) {
+        Pix pp;
+        pp.wo = tid;
+        pp.w = l.w + tid;
+        pp.rt = l.tile + g.tb;
+        return pp;
+    }
+    static __device__ __forceinline__ void invariants(const KViews &kv, const PatchLds &l, const LaneGeom &g, Pix &pp,
+                                                      bool lut) {
+        pixel_patch(kv, l.tile, g.tb, g.s, pp, lut ? l.wlut : nullptr);
+    }
+    static __device__ __forceinline__ float ncc(const KViews &kv, const Pix &pp, int v, int px, int py, float4 h) {
+        return bilateral_ncc<TX>(kv, pp, v, px, py, h);
+    }
+};
+
 // ------------------------------------------------------- texel-form units
 // The templated kernels (k_init, k_sweep_f, k_eval_costs) are instantiated
 // per texel form (a kTx* bit set) in their own translation unit:
@@ -987,5 +1038,23 @@ hipError_t tx_launch_eval(const KViews *d_kv, int nsrc, dim3 grid, hipStream_t s
                                               float *, uint32_t *);
 ACMMP_TX_FORMS(ACMMP_TX_DECL)
 #undef ACMMP_TX_DECL
+
+// The general-patch kernels (k_init_g, k_sweep_g, k_eval_costs_g) are the same
+// file compiled with -DACMMP_GENERAL_UNIT, again one unit per form (the
+// Makefile's GX_FORMS): every form but the texture_filter8 ones.
+#define ACMMP_GX_FORMS(X) X(0) X(1) X(2) X(3) X(4) X(5)
+template <int TX> hipError_t gx_launch_init(const KViews *d_kv, int nsrc, dim3 grid, hipStream_t s, KState st);
+template <int TX>
+hipError_t gx_launch_sweep(const KViews *d_kv, int nsrc, dim3 grid, hipStream_t s, KState st, int colour, int iter);
+template <int TX>
+hipError_t gx_launch_eval(const KViews *d_kv, int nsrc, dim3 grid, hipStream_t s, const float4 *planes, float *out,
+                          float *out_init, uint32_t *out_views);
+#define ACMMP_GX_DECL(TX)                                                                                      \
+    template <> hipError_t gx_launch_init<TX>(const KViews *, int, dim3, hipStream_t, KState);                  \
+    template <> hipError_t gx_launch_sweep<TX>(const KViews *, int, dim3, hipStream_t, KState, int, int);       \
+    template <> hipError_t gx_launch_eval<TX>(const KViews *, int, dim3, hipStream_t, const float4 *, float *,  \
+                                              float *, uint32_t *);
+ACMMP_GX_FORMS(ACMMP_GX_DECL)
+#undef ACMMP_GX_DECL
 
 }  // namespace acmmp

@@ -294,6 +294,24 @@ ViewRel view_rel(const acmmp_camera &rc, const acmmp_camera &sc) {
     return r;
 }
 
+// The patch geometries the kernels are built for. 11 / 2 (the reference
+// defaults, src/ACMMP.h:34,37) runs the fast kernels, every other geometry of
+// the envelope the general ones (acmmp_general.h), whose reference window is
+// sized for radius 10 and whose loop needs at least two taps per axis.
+// texture_filter8 (a fidelity-study mode) is built for 11 / 2 only.
+static bool default_patch(const acmmp_params &p) { return p.patch_size == 11 && p.radius_increment == 2; }
+int check_patch(acmmp_ctx *ctx) {
+    const acmmp_params &p = ctx->prm;
+    const bool inside = p.patch_size > 0 && p.radius_increment > 0 &&
+                        acmmp_patch_geometry_supported(p.patch_size, p.radius_increment);
+    if (inside && (default_patch(p) || !p.texture_filter8)) return ACMMP_OK;
+    return set_err(ctx, ACMMP_ERR_UNSUPPORTED,
+                   "patch_size=%d radius_increment=%d texture_filter8=%d outside the built envelope: "
+                   "1 <= patch_size / 2 <= 10, 1 <= radius_increment <= 2 * (patch_size / 2), "
+                   "texture_filter8 only with patch_size 11 / radius_increment 2",
+                   p.patch_size, p.radius_increment, p.texture_filter8);
+}
+
 // Rebuilds the device-side constant block from the context.
 int kv_upload(acmmp_ctx *ctx) {
     KViews &kv = ctx->h_kv;
@@ -329,7 +347,15 @@ int kv_upload(acmmp_ctx *ctx) {
     if (const char *e = std::getenv("ACMMP_WIDE_INDEX"))
         if (e[0] == '1') kv.wide = 1;
     kv.texel = ctx->pad_texel;
-    if (kv.texel == kTexelU8) {  // bilateral weights of the 256 colour differences (KViews::wlut)
+    // ACMMP_GENERAL_PATCH=1 sends 11 / 2 through the general kernels as well
+    // (parity test and like-for-like timing; not with texture_filter8, which
+    // only the fast kernels have)
+    kv.general = !default_patch(kv.prm);
+    if (const char *e = std::getenv("ACMMP_GENERAL_PATCH"))
+        if (e[0] == '1' && !kv.prm.texture_filter8) kv.general = 1;
+    // bilateral weights of the 256 colour differences (KViews::wlut): its
+    // distance classes are those of 11 / 2, and only the fast kernels read it
+    if (kv.texel == kTexelU8 && !kv.general) {
         const float ss = kv.prm.sigma_spatial, sc = kv.prm.sigma_color;
         for (int a = 0; a < 3; ++a)
             for (int b = a; b < 3; ++b) {
@@ -509,11 +535,7 @@ int set_images_impl(acmmp_ctx *ctx, int num_images, const acmmp_camera *cams, co
     if (num_images < 2 || num_images > ACMMP_MAX_IMAGES)
         return set_err(ctx, ACMMP_ERR_ARG, "num_images=%d outside [2, %d]", num_images, ACMMP_MAX_IMAGES);
     if (!cams || !images) return set_err(ctx, ACMMP_ERR_ARG, "cams/images NULL");
-    if (ctx->prm.patch_size != 11 || ctx->prm.radius_increment != 2)
-        return set_err(ctx, ACMMP_ERR_UNSUPPORTED,
-                       "patch_size=%d radius_increment=%d: kernels are built for the reference "
-                       "defaults 11/2 (src/ACMMP.h:34,37)",
-                       ctx->prm.patch_size, ctx->prm.radius_increment);
+    if (const int rc = check_patch(ctx)) return rc;
     for (int i = 0; i < num_images; ++i) {
         if (!images[i]) return set_err(ctx, ACMMP_ERR_ARG, "image %d is NULL", i);
         if (cams[i].width < 2 || cams[i].height < 1)
@@ -995,8 +1017,7 @@ int prepare_run(acmmp_ctx *ctx) {
     if (p.hierarchy && !ctx->have_scaled)
         return set_err(ctx, ACMMP_ERR_STATE, "hierarchy needs acmmp_set_hierarchy_inputs");
     if (p.seeded && !ctx->have_seed) return set_err(ctx, ACMMP_ERR_STATE, "seeded needs acmmp_set_seed_prior");
-    if (p.patch_size != 11 || p.radius_increment != 2)
-        return set_err(ctx, ACMMP_ERR_UNSUPPORTED, "only patch_size 11 / radius_increment 2 are built");
+    if ((rc = check_patch(ctx))) return rc;
     if (p.max_iterations < 0) return set_err(ctx, ACMMP_ERR_ARG, "max_iterations < 0");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     rc = kv_upload(ctx);
@@ -1182,6 +1203,7 @@ int acmmp_eval_costs(acmmp_ctx *ctx, const float *planes4, float *out_costs, flo
     int rc = check_ready(ctx);
     if (rc) return rc;
     if (!planes4) return set_err(ctx, ACMMP_ERR_ARG, "planes NULL");
+    if ((rc = check_patch(ctx))) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     rc = kv_upload(ctx);
     if (rc) return rc;

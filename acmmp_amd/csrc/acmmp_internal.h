@@ -74,7 +74,11 @@ struct KViews {
     // class (|dx|, |dy|) in {1, 3, 5}^2 up to order (kWlutClasses), formed on
     // the host by the kernel's own float expression (same operations, same
     // order: bit-identical to computing it per tap).
+    // (valid only for patch_size 11 / radius_increment 2; not built otherwise)
     float wlut[6][256];
+    // The general-patch kernels run this problem: any geometry but 11 / 2, or
+    // 11 / 2 with ACMMP_GENERAL_PATCH=1 (parity test, like-for-like timing).
+    int general;
 };
 constexpr int kWlutClasses = 6;
 // distance class of |dx|, |dy| in {1, 3, 5}: (a, b) = ((|dx| - 1) / 2, (|dy| - 1) / 2), unordered

@@ -1,8 +1,8 @@
 // acmmp_kernels.hip — the plain (non-templated) MI355X kernels of
 // ACMMP::RunPatchMatch and every kernel launcher. The templated PatchMatch
 // kernels live in acmmp_kernels_tx.hip, one translation unit per texel form;
-// launch_init / launch_sweep / launch_eval_costs pick the form here
-// (tx_dispatch). Shared device helpers: acmmp_dev.h.
+// launch_init / launch_sweep / launch_eval_costs pick the form and the patch
+// policy here (tx_dispatch, gx_dispatch). Shared device helpers: acmmp_dev.h.
 #include <type_traits>
 
 #include "acmmp_dev.h"
@@ -276,6 +276,19 @@ static hipError_t tx_dispatch(const KViews &h_kv, F f) {
     }
 }
 
+// The same for the general-patch units (KViews::general), one case per form
+// of ACMMP_GX_FORMS.
+template <typename F>
+static hipError_t gx_dispatch(const KViews &h_kv, F f) {
+    switch (tx_form(h_kv)) {
+#define ACMMP_GX_CASE(TX) \
+    case TX: return f(std::integral_constant<int, TX>{});
+        ACMMP_GX_FORMS(ACMMP_GX_CASE)
+#undef ACMMP_GX_CASE
+        default: return hipErrorNotSupported;  // texture_filter8 is an 11 / 2 mode
+    }
+}
+
 // Colour-split grid over image rows [st.y0, st.y1): whole blocks of kBY
 // rows from the block row holding y0 (the kernels skip rows outside).
 static dim3 cs_grid(const KViews &kv, const KState &st, int colours) {
@@ -289,6 +302,10 @@ static dim3 row_grid(int cols, const KState &st) {
 
 hipError_t launch_init(const KViews *d_kv, const KViews &h_kv, const KState &st, hipStream_t stream) {
     if (st.y1 <= st.y0) return hipSuccess;
+    if (h_kv.general)
+        return gx_dispatch(h_kv, [&](auto tx) {
+            return gx_launch_init<decltype(tx)::value>(d_kv, h_kv.nsrc, cs_grid(h_kv, st, 2), stream, st);
+        });
     return tx_dispatch(h_kv, [&](auto tx) {
         return tx_launch_init<decltype(tx)::value>(d_kv, h_kv.nsrc, cs_grid(h_kv, st, 2), stream, st);
     });
@@ -297,6 +314,11 @@ hipError_t launch_init(const KViews *d_kv, const KViews &h_kv, const KState &st,
 hipError_t launch_sweep(const KViews *d_kv, const KViews &h_kv, const KState &st, int colour, int iter,
                         hipStream_t stream) {
     if (st.y1 <= st.y0) return hipSuccess;
+    if (h_kv.general)
+        return gx_dispatch(h_kv, [&](auto tx) {
+            return gx_launch_sweep<decltype(tx)::value>(d_kv, h_kv.nsrc, cs_grid(h_kv, st, 1), stream, st, colour,
+                                                        iter);
+        });
     return tx_dispatch(h_kv, [&](auto tx) {
         return tx_launch_sweep<decltype(tx)::value>(d_kv, h_kv.nsrc, cs_grid(h_kv, st, 1), stream, st, colour, iter);
     });
@@ -319,6 +341,11 @@ hipError_t launch_eval_costs(const KViews *d_kv, const KViews &h_kv, const float
                              float *out_init, uint32_t *out_views, hipStream_t stream) {
     KState all{};
     all.y1 = h_kv.H;
+    if (h_kv.general)
+        return gx_dispatch(h_kv, [&](auto tx) {
+            return gx_launch_eval<decltype(tx)::value>(d_kv, h_kv.nsrc, cs_grid(h_kv, all, 2), stream, planes, out,
+                                                       out_init, out_views);
+        });
     return tx_dispatch(h_kv, [&](auto tx) {
         return tx_launch_eval<decltype(tx)::value>(d_kv, h_kv.nsrc, cs_grid(h_kv, all, 2), stream, planes, out,
                                                    out_init, out_views);

@@ -1,30 +1,43 @@
-// acmmp_kernels_tx.hip — the templated PatchMatch kernels (k_init, k_sweep_f,
-// k_eval_costs) of ONE texel form: compiled once per form with
-// -DACMMP_TX_UNIT=<form> (a kTx* bit set, acmmp_dev.h; the Makefile's
-// TX_FORMS), 5 source-count buckets each. The three tx_launch_* functions at
-// the end are the unit's entry points; acmmp_kernels.hip picks the form.
+// acmmp_kernels_tx.hip — the templated PatchMatch kernels of ONE texel form
+// and ONE patch policy: compiled once per form with -DACMMP_TX_UNIT=<form> (a
+// kTx* bit set, acmmp_dev.h; the Makefile's TX_FORMS) for the 11 / 2 fast path
+// (k_init, k_sweep_f, k_eval_costs over FastPatch), and once more per form with
+// -DACMMP_GENERAL_UNIT (GX_FORMS) for every other patch geometry (k_init_g,
+// k_sweep_g, k_eval_costs_g over GeneralPatch), 5 source-count buckets each.
+// The kernel bodies (init_body, sweep_body, refine_costs_compact, eval_body)
+// are written once over the policy. The three tx_launch_* (gx_launch_*)
+// functions at the end are the unit's entry points; acmmp_kernels.hip picks
+// the form and the policy.
 #ifndef ACMMP_TX_UNIT
 #error "compile with -DACMMP_TX_UNIT=<texel form> (see the Makefile's TX_FORMS)"
 #endif
 
 #include "acmmp_dev.h"
+#ifdef ACMMP_GENERAL_UNIT
+#include "acmmp_general.h"
+#endif
 
 namespace acmmp {
+
+// The block's LDS arrays of policy P (reference window, weight slots, weight
+// table), declared in the calling body.
+#define ACMMP_PATCH_LDS(P, lds)                            \
+    __shared__ float tile[P::kTileFloats];                 \
+    __shared__ WSlot wlds[P::kWeightSlots];                \
+    __shared__ float wlut[P::kLutFloats];                  \
+    const PatchLds lds = {tile, wlds, wlut}
 
 // ------------------------------------------------------------------ init
 // RandomInitialization (src/ACMMP.cu:609-705). Reads the row-major state,
 // writes the colour-split "current" buffers. blockIdx.z = colour.
-template <int NS, int TX>
-__global__ __launch_bounds__(kThreads) void k_init(const KViews *__restrict__ kvp, KState st) {
-    __shared__ float tile[kTileW * kTileH];
-    __shared__ WSlot wlds[kSlots * kThreads];
-    constexpr bool kLut = (TX & kTxU8) != 0;  // bilateral weights from the u8-form table (KViews::wlut)
-    __shared__ float wlut[kLut ? kWlutClasses * 256 : 1];
+template <int NS, typename P>
+DEV void init_body(const KViews *__restrict__ kvp, KState st) {
+    ACMMP_PATCH_LDS(P, lds);
+    constexpr bool kLut = P::kLutFloats > 1;  // bilateral weights from the u8-form table (KViews::wlut)
     const KViews &kv = *kvp;
     const int colour = blockIdx.z;
     const BlockXY blk = xcd_block(st.y0 / kBY);
-    load_ref_tile(kv, tile, blk.bx * kBX, blk.by * kBY, colour);
-    if (kLut) load_wlut(kv, wlut);
+    P::stage(kv, lds, blk, colour, kLut);
     __syncthreads();
     const LaneGeom g = lane_geom(colour, blk);
     const int px = g.px, py = g.py;
@@ -33,11 +46,8 @@ __global__ __launch_bounds__(kThreads) void k_init(const KViews *__restrict__ kv
     const acmmp_camera &c0 = kv.cam[0];
     const int center = py * kv.W + px;
     dm_rng rs = make_rng(kv, center, 0u);
-    PixPatch pp;
-    pp.wo = threadIdx.y * kBX + threadIdx.x;
-    pp.w = wlds + pp.wo;
-    pp.rt = tile + g.tb;
-    pixel_patch(kv, tile, g.tb, g.s, pp, kLut ? wlut : nullptr);
+    typename P::Pix pp = P::lane(lds, g, blk, threadIdx.y * kBX + threadIdx.x);
+    P::invariants(kv, lds, g, pp, kLut);
     float4 plane;
     float cost;
     uint32_t sel = 0;
@@ -45,10 +55,10 @@ __global__ __launch_bounds__(kThreads) void k_init(const KViews *__restrict__ kv
         const float depth = dm_rng_uniform(&rs) * (prm.depth_max - prm.depth_min) + prm.depth_min;
         plane = random_normal(c0, px, py, rs, depth);
         plane.w = distance_to_origin(c0, px, py, depth, plane);
-        cost = initial_cost<NS, TX>(kv, tile, g.tb, pp, px, py, plane, sel);
+        cost = initial_cost<NS, P>(kv, pp, px, py, plane, sel);
     } else if (prm.seeded) {
         plane = st.seed[center];
-        cost = initial_cost<NS, TX>(kv, tile, g.tb, pp, px, py, plane, sel);
+        cost = initial_cost<NS, P>(kv, pp, px, py, plane, sel);
     } else if (prm.planar_prior) {
         if (st.mask[center] > 0 && st.rm_cost[center] >= 0.1f) {
             const float perturbation = 0.02f;
@@ -63,7 +73,7 @@ __global__ __launch_bounds__(kThreads) void k_init(const KViews *__restrict__ kv
             plane = st.rm_plane[center];
             plane.w = distance_to_origin(c0, px, py, plane.w, plane);
         }
-        cost = initial_cost<NS, TX>(kv, tile, g.tb, pp, px, py, plane, sel);
+        cost = initial_cost<NS, P>(kv, pp, px, py, plane, sel);
     } else if (prm.upsample) {
         const float scale = (float)(1.0 * (double)prm.scaled_cols / (double)kv.W);
         const float sigmad = 0.50f, sigmar = 25.5f;
@@ -75,16 +85,16 @@ __global__ __launch_bounds__(kThreads) void k_init(const KViews *__restrict__ kv
         float ucost;
         const float4 n_total = upscale_normal(kv, st, px, py, sigmad, sigmar, nn, o_y, o_x, refPix, ucost);
         const float4 prev = st.rm_plane[center];
-        st.pre_cost[center] = initial_cost<NS, TX>(kv, tile, g.tb, pp, px, py, prev, sel);
+        st.pre_cost[center] = initial_cost<NS, P>(kv, pp, px, py, prev, sel);
         plane = to_cam(c0, n_total);
         plane.w = distance_to_origin(c0, px, py, prev.w, plane);
-        cost = initial_cost<NS, TX>(kv, tile, g.tb, pp, px, py, plane, sel);
+        cost = initial_cost<NS, P>(kv, pp, px, py, plane, sel);
     } else {
         float4 h = prm.hierarchy ? st.scaled[center] : st.rm_plane[center];
         h = to_cam(c0, h);
         h.w = distance_to_origin(c0, px, py, h.w, h);
         plane = h;
-        cost = initial_cost<NS, TX>(kv, tile, g.tb, pp, px, py, plane, sel);
+        cost = initial_cost<NS, P>(kv, pp, px, py, plane, sel);
     }
     const int ci = py * kv.Wh + g.k;
     st.plane[colour][ci] = plane;
@@ -161,8 +171,8 @@ DEV void wave_sync() {
 // accept rule is another one, come with `prunable` false (a flag rather than
 // a NaN bound: the select's extra VGPR put the NS 9 kernel 16 B of scratch
 // over what tests/test_isa_guards.py allows).
-template <int TX, typename RD, typename RN>
-DEV void refine_costs_compact(const KViews &kv, const float *tile, WSlot *wlds, float4 *lds, const PixPatch &pp,
+template <typename P, typename RD, typename RN>
+DEV void refine_costs_compact(const KViews &kv, const PatchLds &plds, float4 *lds, const typename P::Pix &pp,
                               const ViewCounts &vw, int nsrc, int colour, BlockXY blk, RD ref_depth,
                               RN ref_normal, int px, int py, float weight_norm, float bound, bool prunable) {
     const acmmp_camera &c0 = kv.cam[0];
@@ -209,10 +219,7 @@ DEV void refine_costs_compact(const KViews &kv, const float *tile, WSlot *wlds, 
                 const int t = item >> 6;
                 const int otid = wbase + (item & 63);
                 const LaneGeom og = lane_geom_of(colour, blk, otid);
-                PixPatch op;
-                op.wo = otid;
-                op.w = wlds + otid;
-                op.rt = tile + og.tb;
+                typename P::Pix op = P::lane(plds, og, blk, otid);
                 op.mean = cmp_pd(lds, 1, otid);
                 op.var = cmp_pd(lds, 2, otid);
                 op.inv_wsum = cmp_pd(lds, 3, otid);
@@ -220,7 +227,7 @@ DEV void refine_costs_compact(const KViews &kv, const float *tile, WSlot *wlds, 
                 // the geometric depth fetch goes out ahead of the NCC's gathers
                 GeomFetch gf = {};
                 if (kv.prm.geom_consistency) gf = geom_fetch(kv, j + 1, geom_ref(kv, h, og.px, og.py));
-                const float cc = bilateral_ncc<TX>(kv, tile, og.tb, op, j + 1, og.px, og.py, h);
+                const float cc = P::ncc(kv, op, j + 1, og.px, og.py, h);
                 cmp_res(lds, t, otid) =
                     kv.prm.geom_consistency ? cc + 0.2f * geom_finish(kv, j + 1, gf, og.px, og.py) : cc;
             }
@@ -252,17 +259,14 @@ DEV void refine_costs_compact(const KViews &kv, const float *tile, WSlot *wlds, 
 // half-sweep snapshot); own state lives in registers and is written to the
 // "next" buffer of this colour. (A device function rather than the kernel
 // body: measured 4.15 -> 4.05 ms per launch)
-template <int NS, int TX>
+template <int NS, typename P>
 DEV void sweep_body(const KViews *__restrict__ kvp, KState st, int colour, int iter) {
-    __shared__ float tile[kTileW * kTileH];
-    __shared__ WSlot wlds[kSlots * kThreads];
+    ACMMP_PATCH_LDS(P, lds);
     __shared__ float4 cand_lds[8 * kThreads];
-    constexpr bool kLut = (TX & kTxU8) != 0;  // bilateral weights from the u8-form table (KViews::wlut)
-    __shared__ float wlut[kLut ? kWlutClasses * 256 : 1];
+    constexpr bool kLut = P::kLutFloats > 1;  // bilateral weights from the u8-form table (KViews::wlut)
     const KViews &kv = *kvp;
     const BlockXY blk = xcd_block(st.y0 / kBY);
-    load_ref_tile(kv, tile, blk.bx * kBX, blk.by * kBY, colour);
-    if (kLut) load_wlut(kv, wlut);
+    P::stage(kv, lds, blk, colour, kLut);
     __syncthreads();
     const LaneGeom g = lane_geom(colour, blk);
     const int px = g.px, py = g.py;
@@ -387,11 +391,8 @@ DEV void sweep_body(const KViews *__restrict__ kvp, KState st, int colour, int i
     for (int d = 0; d < 8; ++d) cand_slot[d * kThreads] = cpl[d];
     auto cand = [&](int d) -> float4 { return cand_slot[d * kThreads]; };
 
-    PixPatch pp;
-    pp.wo = threadIdx.y * kBX + threadIdx.x;
-    pp.w = wlds + pp.wo;
-    pp.rt = tile + g.tb;
-    pixel_patch(kv, tile, g.tb, g.s, pp, kLut ? wlut : nullptr);
+    typename P::Pix pp = P::lane(lds, g, blk, threadIdx.y * kBX + threadIdx.x);
+    P::invariants(kv, lds, g, pp, kLut);
 
     // cost_array[8][32] = {2.0f}: only [0][0] is 2, the rest 0 (:805)
     float cost_array[8][NS];
@@ -420,7 +421,7 @@ DEV void sweep_body(const KViews *__restrict__ kvp, KState st, int colour, int i
 #pragma unroll 1
         for (int d = 0; d < 8; ++d) {
             float c;
-            if ((flags >> d) & 1u) c = bilateral_ncc<TX>(kv, tile, g.tb, pp, v + 1, px, py, cand(d));
+            if ((flags >> d) & 1u) c = P::ncc(kv, pp, v + 1, px, py, cand(d));
             else c = (d == 0 && v == 0) ? 2.0f : 0.0f;
             cost_array[d][v] = c;
             if (c < cost_threshold) {
@@ -607,8 +608,8 @@ DEV void sweep_body(const KViews *__restrict__ kvp, KState st, int colour, int i
         // planar-prior lane accepts by exp(-c^2 / beta) * prior instead and
         // may raise cost_now: it keeps all its hypotheses
         if (t == 1)
-            refine_costs_compact<TX>(kv, tile, wlds, cand_lds, pp, vw, nsrc, colour, blk, ref_depth, ref_normal,
-                                     px, py, weight_norm, cost_now, !has_prior);
+            refine_costs_compact<P>(kv, lds, cand_lds, pp, vw, nsrc, colour, blk, ref_depth, ref_normal, px, py,
+                                    weight_norm, cost_now, !has_prior);
         float4 h;
         if (t == 0) h = my_plane;
         else h = cand_lds[(t - 1) * kThreads + pp.wo];  // stored by refine_costs_compact
@@ -626,7 +627,7 @@ DEV void sweep_body(const KViews *__restrict__ kvp, KState st, int colour, int i
                     // the geometric depth fetch goes out ahead of the NCC's gathers
                     GeomFetch gf = {};
                     if (prm.geom_consistency) gf = geom_fetch(kv, j + 1, gnow);
-                    const float c = bilateral_ncc<TX>(kv, tile, g.tb, pp, j + 1, px, py, h);
+                    const float c = P::ncc(kv, pp, j + 1, px, py, h);
                     if (prm.geom_consistency) tc += wj * (c + 0.2f * geom_finish(kv, j + 1, gf, px, py));
                     else tc += wj * c;
                 }
@@ -759,42 +760,72 @@ DEV void sweep_body(const KViews *__restrict__ kvp, KState st, int colour, int i
     st.sv[colour][my] = my_sv;
 }
 
-template <int NS, int TX>
-__global__ __launch_bounds__(kThreads, kSweepWaves) void k_sweep_f(const KViews *__restrict__ kvp, KState st,
-                                                                   int colour, int iter) {
-    sweep_body<NS, TX>(kvp, st, colour, iter);
-}
-
 // T1 kernel: costs of a given plane per pixel against every source view
 // (same NCC code path as the sweep; blockIdx.z = colour).
-template <int NS, int TX>
-__global__ __launch_bounds__(kThreads) void k_eval_costs(const KViews *__restrict__ kvp, const float4 *planes,
-                                                         float *out, float *out_init, uint32_t *out_views) {
-    __shared__ float tile[kTileW * kTileH];
-    __shared__ WSlot wlds[kSlots * kThreads];
+template <int NS, typename P>
+DEV void eval_body(const KViews *__restrict__ kvp, const float4 *planes, float *out, float *out_init,
+                   uint32_t *out_views) {
+    ACMMP_PATCH_LDS(P, lds);
     const KViews &kv = *kvp;
     const int colour = blockIdx.z;
     const BlockXY blk = xcd_block();
-    load_ref_tile(kv, tile, blk.bx * kBX, blk.by * kBY, colour);
+    P::stage(kv, lds, blk, colour, false);  // (weights computed, not from the table)
     __syncthreads();
     const LaneGeom g = lane_geom(colour, blk);
     if (g.px >= kv.W || g.py >= kv.H) return;
     const int c = g.py * kv.W + g.px;
-    PixPatch pp;
-    pp.wo = threadIdx.y * kBX + threadIdx.x;
-    pp.w = wlds + pp.wo;
-    pp.rt = tile + g.tb;
-    pixel_patch(kv, tile, g.tb, g.s, pp);
+    typename P::Pix pp = P::lane(lds, g, blk, threadIdx.y * kBX + threadIdx.x);
+    P::invariants(kv, lds, g, pp, false);
     const float4 h = planes[c];
     if (out)
-        for (int v = 0; v < kv.nsrc; ++v)
-            out[(size_t)c * kv.nsrc + v] = bilateral_ncc<TX>(kv, tile, g.tb, pp, v + 1, g.px, g.py, h);
+        for (int v = 0; v < kv.nsrc; ++v) out[(size_t)c * kv.nsrc + v] = P::ncc(kv, pp, v + 1, g.px, g.py, h);
     if (out_init) {
         uint32_t sel = 0;
-        out_init[c] = initial_cost<NS, TX>(kv, tile, g.tb, pp, g.px, g.py, h, sel);
+        out_init[c] = initial_cost<NS, P>(kv, pp, g.px, g.py, h, sel);
         if (out_views) out_views[c] = sel;
     }
 }
+
+// ------------------------------------------------------------ the kernels
+#ifndef ACMMP_GENERAL_UNIT
+template <int NS, int TX>
+__global__ __launch_bounds__(kThreads) void k_init(const KViews *__restrict__ kvp, KState st) {
+    init_body<NS, FastPatch<TX>>(kvp, st);
+}
+template <int NS, int TX>
+__global__ __launch_bounds__(kThreads, kSweepWaves) void k_sweep_f(const KViews *__restrict__ kvp, KState st,
+                                                                   int colour, int iter) {
+    sweep_body<NS, FastPatch<TX>>(kvp, st, colour, iter);
+}
+template <int NS, int TX>
+__global__ __launch_bounds__(kThreads) void k_eval_costs(const KViews *__restrict__ kvp, const float4 *planes,
+                                                         float *out, float *out_init, uint32_t *out_views) {
+    eval_body<NS, FastPatch<TX>>(kvp, planes, out, out_init, out_views);
+}
+#define ACMMP_K_INIT k_init
+#define ACMMP_K_SWEEP k_sweep_f
+#define ACMMP_K_EVAL k_eval_costs
+#define ACMMP_LAUNCH(name) tx_launch_##name
+#else
+template <int NS, int TX>
+__global__ __launch_bounds__(kThreads) void k_init_g(const KViews *__restrict__ kvp, KState st) {
+    init_body<NS, GeneralPatch<TX>>(kvp, st);
+}
+template <int NS, int TX>
+__global__ __launch_bounds__(kThreads, kSweepWaves) void k_sweep_g(const KViews *__restrict__ kvp, KState st,
+                                                                   int colour, int iter) {
+    sweep_body<NS, GeneralPatch<TX>>(kvp, st, colour, iter);
+}
+template <int NS, int TX>
+__global__ __launch_bounds__(kThreads) void k_eval_costs_g(const KViews *__restrict__ kvp, const float4 *planes,
+                                                           float *out, float *out_init, uint32_t *out_views) {
+    eval_body<NS, GeneralPatch<TX>>(kvp, planes, out, out_init, out_views);
+}
+#define ACMMP_K_INIT k_init_g
+#define ACMMP_K_SWEEP k_sweep_g
+#define ACMMP_K_EVAL k_eval_costs_g
+#define ACMMP_LAUNCH(name) gx_launch_##name
+#endif
 
 // Source-view count -> array capacity of the templated kernels.
 static int ns_bucket(int nsrc) {
@@ -815,20 +846,21 @@ static int ns_bucket(int nsrc) {
     }
 
 template <>
-hipError_t tx_launch_init<ACMMP_TX_UNIT>(const KViews *d_kv, int nsrc, dim3 grid, hipStream_t s, KState st) {
-    ACMMP_NS_SWITCH(k_init, grid, s, d_kv, st);
+hipError_t ACMMP_LAUNCH(init)<ACMMP_TX_UNIT>(const KViews *d_kv, int nsrc, dim3 grid, hipStream_t s, KState st) {
+    ACMMP_NS_SWITCH(ACMMP_K_INIT, grid, s, d_kv, st);
     return hipGetLastError();
 }
 template <>
-hipError_t tx_launch_sweep<ACMMP_TX_UNIT>(const KViews *d_kv, int nsrc, dim3 grid, hipStream_t s, KState st,
-                                          int colour, int iter) {
-    ACMMP_NS_SWITCH(k_sweep_f, grid, s, d_kv, st, colour, iter);
+hipError_t ACMMP_LAUNCH(sweep)<ACMMP_TX_UNIT>(const KViews *d_kv, int nsrc, dim3 grid, hipStream_t s, KState st,
+                                              int colour, int iter) {
+    ACMMP_NS_SWITCH(ACMMP_K_SWEEP, grid, s, d_kv, st, colour, iter);
     return hipGetLastError();
 }
 template <>
-hipError_t tx_launch_eval<ACMMP_TX_UNIT>(const KViews *d_kv, int nsrc, dim3 grid, hipStream_t s,
-                                         const float4 *planes, float *out, float *out_init, uint32_t *out_views) {
-    ACMMP_NS_SWITCH(k_eval_costs, grid, s, d_kv, planes, out, out_init, out_views);
+hipError_t ACMMP_LAUNCH(eval)<ACMMP_TX_UNIT>(const KViews *d_kv, int nsrc, dim3 grid, hipStream_t s,
+                                             const float4 *planes, float *out, float *out_init,
+                                             uint32_t *out_views) {
+    ACMMP_NS_SWITCH(ACMMP_K_EVAL, grid, s, d_kv, planes, out, out_init, out_views);
     return hipGetLastError();
 }
 

@@ -31,6 +31,9 @@ void usage() {
         "  --device N               HIP device (default 0)\n"
         "  --iterations N           PatchMatch iterations per run (default: the reference's 2)\n"
         "  --seed N                 base RNG seed (default 1234)\n"
+        "  --patch_size N           PatchMatch patch size (default 11); with --radius_increment inside\n"
+        "                           1 <= N / 2 <= 10, honoured by both pass orders and --view_parallel\n"
+        "  --radius_increment N     step between patch samples (default 2), 1 <= N <= 2 * (patch_size / 2)\n"
         "  --no_triangulation       do not write triangulation.png\n"
         "  --quiet                  no progress output\n"
         "  -f, --fuse_thresh X      average inverse score threshold for fusion (0.3)\n"
@@ -69,6 +72,7 @@ int main(int argc, char **argv) {
     float consistency_scalar = 0.3f;
     int num_consistent_thresh = 1, single_match_penalty = 0;
     int device = 0, iterations = 0, concurrent_views = 2;
+    int patch_size = 0, radius_increment = 0;  // 0: the defaults, 11 / 2
     bool device_set = false, view_parallel = false, exchange_rccl = true, exchange_auto = true, split_tail = true;
     unsigned seed = 1234;
     for (int i = 1; i < argc; ++i) {
@@ -117,6 +121,12 @@ int main(int argc, char **argv) {
             concurrent_views = std::atoi(value().c_str());
         } else if (a == "--iterations") {
             iterations = std::atoi(value().c_str());
+        } else if (a == "--patch_size") {
+            patch_size = std::atoi(value().c_str());
+            if (patch_size <= 0) patch_size = -1;  // (0 would mean "default": a given value must be valid)
+        } else if (a == "--radius_increment") {
+            radius_increment = std::atoi(value().c_str());
+            if (radius_increment <= 0) radius_increment = -1;
         } else if (a == "--seed") {
             seed = (unsigned)std::strtoul(value().c_str(), nullptr, 10);
         } else if (a == "--no_triangulation") {
@@ -152,6 +162,13 @@ int main(int argc, char **argv) {
         usage();
         return 2;
     }
+    if (!acmmp_patch_geometry_supported(patch_size, radius_increment)) {  // before any file or device is touched
+        std::fprintf(stderr,
+                     "acmmp_main: --patch_size %d --radius_increment %d outside the built envelope: "
+                     "1 <= patch_size / 2 <= 10, 1 <= radius_increment <= 2 * (patch_size / 2)\n",
+                     patch_size ? patch_size : 11, radius_increment ? radius_increment : 2);
+        return 2;
+    }
 
     std::vector<acmmp_problem> problems(4096);
     int num_images = 0;
@@ -178,6 +195,8 @@ int main(int argc, char **argv) {
     opt.max_iterations = iterations;
     opt.write_triangulation = triangulation ? 1 : 0;
     opt.verbose = quiet ? 0 : 1;
+    opt.patch_size = patch_size;
+    opt.radius_increment = radius_increment;
     unsigned pass = 0;
     std::string pass_error;  // the first failing view's message (set by for_views)
     // fn(0..num_images-1), `lanes` views at a time, none started after a
@@ -231,6 +250,8 @@ int main(int argc, char **argv) {
         vo.device = device_set ? device : -1;
         vo.iterations = iterations;
         vo.seed = seed;
+        vo.patch_size = patch_size;
+        vo.radius_increment = radius_increment;
         vo.geom_iterations = geom_iterations;
         vo.concurrent_views = concurrent_views;
         vo.exchange_rccl = exchange_rccl;

@@ -510,6 +510,12 @@ struct PhaseClock {
 };
 }  // namespace
 
+int acmmp_patch_geometry_supported(int patch_size, int radius_increment) {
+    const int ps = patch_size ? patch_size : 11, inc = radius_increment ? radius_increment : 2;
+    const int radius = ps / 2;
+    return ps > 0 && radius >= 1 && radius <= 10 && inc >= 1 && inc <= 2 * radius;
+}
+
 int acmmp_process_problem(const char *dense_folder, const char *output_folder, const acmmp_problem *problems,
                           int count, int idx, const acmmp_pass_options *opt) {
     if (!dense_folder || !output_folder || !problems || !opt || idx < 0 || idx >= count)
@@ -528,6 +534,13 @@ int acmmp_process_problem(const char *dense_folder, const char *output_folder, c
         p.seed_lo = opt->seed_lo;
         p.seed_hi = opt->seed_hi;
         if (opt->max_iterations > 0) p.max_iterations = opt->max_iterations;
+        if (!acmmp_patch_geometry_supported(opt->patch_size, opt->radius_increment))
+            return fail(ACMMP_ERR_UNSUPPORTED,
+                        "patch_size=%d radius_increment=%d outside the built envelope: 1 <= patch_size / 2 <= 10, "
+                        "1 <= radius_increment <= 2 * (patch_size / 2)",
+                        opt->patch_size, opt->radius_increment);
+        if (opt->patch_size) p.patch_size = opt->patch_size;  // 0: the default, 11 / 2
+        if (opt->radius_increment) p.radius_increment = opt->radius_increment;
         acmmp.set_params(p);
         std::vector<acmmp::Problem> all(problems, problems + count);
         acmmp.InputInitialization(dense_folder, output_folder, all, idx);

@@ -647,6 +647,8 @@ class Driver {
         p.seed_lo = o_.seed + (unsigned)problems_[(size_t)v].ref_image_id;
         p.seed_hi = (unsigned)pass_index_;
         if (o_.iterations > 0) p.max_iterations = o_.iterations;
+        if (o_.patch_size) p.patch_size = o_.patch_size;
+        if (o_.radius_increment) p.radius_increment = o_.radius_increment;
         return p;
     }
 

@@ -9,6 +9,8 @@ struct VpOptions {
     std::string output_dir = "/ACMMP";
     int device = -1;                  // HIP device; -1 = LOCAL_RANK
     int iterations = 0;               // > 0 overrides max_iterations of every run
+    int patch_size = 0;               // PatchMatch patch geometry of every run; 0: the defaults 11 / 2
+    int radius_increment = 0;
     unsigned seed = 1234;             // RNG key of view v: seed + ref id, pass index
     int geom_iterations = 2;          // geometric passes per scale (src/main_ACMMP.cpp:109)
     int concurrent_views = 2;         // engines (HIP streams) per GPU

@@ -134,6 +134,8 @@ class ViewTask:
     state: Optional[tuple] = None          # (planes (H,W,4), costs (H,W)) tensors, geom passes
     hier_inputs: Optional[tuple] = None    # (scaled planes (sh,sw,4), upsampled depth (H,W)) tensors
     textures: Optional[list] = None        # engine.Texture per image (prebuilt footprint records)
+    patch_size: int = 0                    # patch geometry of the run; 0: the defaults 11 / 2
+    radius_increment: int = 0
 
 
 @dataclass
@@ -146,7 +148,8 @@ class ViewResult:
 def _view_params(t: ViewTask) -> _abi.Params:
     """ProcessProblem's parameter set-up (src/acmmp_definitions.cpp:253-268):
     defaults, SetGeomConsistencyParams (geom: 2 iterations, src/ACMMP.cpp:
-    447-454), SetHierarchyParams, the per-view RNG key, -iterations."""
+    447-454), SetHierarchyParams, the per-view RNG key, -iterations, and the
+    patch geometry (0: the defaults 11 / 2)."""
     p = _abi.default_params()
     if t.geom:
         p.geom_consistency = 1
@@ -159,6 +162,10 @@ def _view_params(t: ViewTask) -> _abi.Params:
     p.seed_hi = t.seed_hi & 0xFFFFFFFF
     if t.max_iterations > 0:
         p.max_iterations = t.max_iterations
+    if t.patch_size:
+        p.patch_size = t.patch_size
+    if t.radius_increment:
+        p.radius_increment = t.radius_increment
     return p
 
 
@@ -237,7 +244,10 @@ class ViewParallelPipeline:
                  max_iterations: int = 0, geom_iterations: int = 2, group=None,
                  compute: Optional[Callable] = None, jbu: Optional[Callable] = None, write_outputs: bool = True,
                  comm_device: Optional[torch.device] = None, tensor_device: Optional[torch.device] = None,
-                 concurrent_views: int = 2, timing: bool = False, split_tail: bool = True):
+                 concurrent_views: int = 2, timing: bool = False, split_tail: bool = True,
+                 patch_size: int = 0, radius_increment: int = 0):
+        self.patch_size = patch_size
+        self.radius_increment = radius_increment
         self.dense = dense_folder
         self.output_folder = dense_folder + output_dir
         self.device = device
@@ -398,7 +408,8 @@ class ViewParallelPipeline:
                      textures=[self.textures[i] for i in ids] if self.textures else None,
                      geom=geom, planar=planar, hierarchy=hierarchy,
                      multi=multi, seed_lo=self.seed + p.ref_image_id, seed_hi=self.pass_index,
-                     max_iterations=self.max_iterations)
+                     max_iterations=self.max_iterations, patch_size=self.patch_size,
+                     radius_increment=self.radius_increment)
         if geom:
             t.depths = [self.depths[self.index_of[i]] for i in ids]
             prev = self.state[v]
@@ -559,6 +570,8 @@ def main():
     ap.add_argument("--output_dir", default="/ACMMP")
     ap.add_argument("--iterations", type=int, default=0)
     ap.add_argument("--seed", type=int, default=1234)
+    ap.add_argument("--patch_size", type=int, default=0, help="PatchMatch patch size (default 11)")
+    ap.add_argument("--radius_increment", type=int, default=0, help="step between patch samples (default 2)")
     ap.add_argument("--backend", default=None, help="nccl (RCCL, default with GPUs) or gloo")
     ap.add_argument("--concurrent_views", type=int, default=2,
                     help="views computed at once per GPU (one engine / HIP stream each)")
@@ -571,7 +584,8 @@ def main():
             torch.cuda.set_device(local_rank)
         dist.init_process_group(backend)
     pipe = ViewParallelPipeline(args.dense_folder, args.output_dir, device=local_rank, seed=args.seed,
-                                max_iterations=args.iterations, concurrent_views=args.concurrent_views)
+                                max_iterations=args.iterations, concurrent_views=args.concurrent_views,
+                                patch_size=args.patch_size, radius_increment=args.radius_increment)
     out = pipe.run()
     if pipe.rank == 0:
         print(f"Depth/normal/cost maps written under {out}")

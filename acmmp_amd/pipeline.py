@@ -74,8 +74,12 @@ def prior_plane_estimate(dense_folder: str, cam_num: int, cam, rows: int, cols: 
 
 def pass_options(geom_consistency=False, planar_prior=False, hierarchy=False, multi_geometry=False,
                  device=0, max_iterations=0, seed_lo=1234, seed_hi=0, write_triangulation=True,
-                 verbose=False, seeded=False) -> _abi.PassOptions:
+                 verbose=False, seeded=False, patch_size=0, radius_increment=0) -> _abi.PassOptions:
+    """patch_size / radius_increment: PatchMatchParams' patch geometry for the
+    runs of the pass; 0 means the default (11 / 2)."""
     o = _abi.PassOptions()
+    o.patch_size = int(patch_size)
+    o.radius_increment = int(radius_increment)
     o.seeded = int(seeded)
     o.device = device
     o.geom_consistency = int(geom_consistency)
@@ -120,9 +124,11 @@ def scale_step(problems: list) -> None:
 
 def run_sequential(dense_folder: str, output_dir: str | None = None, device: int = 0, max_iterations: int = 0,
                    seed: int = 1234, write_triangulation: bool = True, geom_iterations: int = 2,
-                   verbose: bool = False, prior: bool = False, concurrent_views: int = 2) -> str:
+                   verbose: bool = False, prior: bool = False, concurrent_views: int = 2,
+                   patch_size: int = 0, radius_increment: int = 0) -> str:
     """main_ACMMP's multi-scale loop without fusion; returns the output folder.
     prior=True is the -p flag: seeded first pass, default folder /ACMMP_PRIOR.
+    patch_size / radius_increment: the patch geometry of every run (0: 11 / 2).
 
     The views of a pass that reads no file written in the same pass (every
     pass but the multi-geometry ones: a first geometric pass reads its
@@ -154,7 +160,8 @@ def run_sequential(dense_folder: str, output_dir: str | None = None, device: int
 
     def run_pass(geom, planar, hier, multi, seeded=False):
         opts = [pass_options(geom, planar, hier, multi, device, max_iterations, seed + p.ref_image_id,
-                             state["pass"], write_triangulation, verbose, seeded) for p in problems]
+                             state["pass"], write_triangulation, verbose, seeded, patch_size, radius_increment)
+                for p in problems]
         for_views(1 if (geom and multi) else concurrent_views,
                   lambda i: process_problem(dense_folder, output_folder, problems, i, opts[i]))
         state["pass"] += 1

@@ -121,8 +121,16 @@ typedef struct acmmp_pass_options {
     uint32_t seed_hi;
     int32_t write_triangulation;/* write 2333_%08d/triangulation.png in planar passes (:310-330) */
     int32_t verbose;            /* print the reference's progress lines to stdout */
-    int32_t reserved[5];
+    int32_t patch_size;         /* PatchMatchParams::patch_size of every run of the pass; 0: the default, 11 */
+    int32_t radius_increment;   /* PatchMatchParams::radius_increment; 0: the default, 2. Outside the built
+                                 * envelope (1 <= patch_size / 2 <= 10, 1 <= radius_increment <=
+                                 * 2 * (patch_size / 2)) the pass returns ACMMP_ERR_UNSUPPORTED */
+    int32_t reserved[3];        /* (the two fields above were reserved[0..1]: zero, as before, means 11 / 2) */
 } acmmp_pass_options;
+
+/* Whether patch_size / radius_increment (0 = default) lie inside the envelope
+ * the kernels are built for. No device is touched. */
+int acmmp_patch_geometry_supported(int patch_size, int radius_increment);
 
 typedef struct acmmp_ctx acmmp_ctx;
 
@@ -312,7 +320,9 @@ int acmmp_synchronize(acmmp_ctx *ctx);
  * its own rows [row_lo, row_hi) of the reference image (the bands tile
  * 0..H). The sweeps compute only those rows; a pixel's CheckerboardPropagation
  * reads neighbour state up to ACMMP_BAND_HALO rows away (the far searches,
- * src/ACMMP.cu:819-826: 3 + 2 * 10 rows), so after every half-sweep the
+ * src/ACMMP.cu:819-826: 3 + 2 * 10 rows; the halo does not depend on
+ * patch_size / radius_increment: a patch reads only the reference image,
+ * which every participant holds whole), so after every half-sweep the
  * engine calls `exchange` with the colour just written: the participant
  * must send its rows [send_*_lo, send_*_hi) of that colour's state to the
  * band above / below and receive theirs into rows [recv_*_lo, recv_*_hi)

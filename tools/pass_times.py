@@ -5,7 +5,13 @@ launch_ms is their mean.
 
 usage: python tools/pass_times.py [reps] > gpurun_out/pass_times.json
 (PASS_NSRC=<n> in the environment: n source views instead of cfg2's 9, so the
-NS 16 / 20 / 32 kernel buckets can be timed.)
+NS 16 / 20 / 32 kernel buckets can be timed. PASS_PATCH=<size>,<inc>:
+patch_size / radius_increment instead of 11 / 2, which runs the general-patch
+kernels; ACMMP_GENERAL_PATCH=1 sends 11 / 2 through them too.
+PASS_VIEWS=<n>: the timed repetitions run the first n reference views only
+(the per-launch mean of fewer launches, for the slow large patches); the
+warm-up repetition still computes every view's depth map, which the geometric
+pass reads.)
 """
 import json
 import os
@@ -20,6 +26,8 @@ from acmmp_amd.resident import EnginePool, geometric_view, photometric_view  # n
 REPS = int(sys.argv[1]) if len(sys.argv) > 1 else 3
 W, H, ITERS = 1600, 1200, 8
 NSRC = int(os.environ.get("PASS_NSRC", "9"))
+VIEWS = int(os.environ.get("PASS_VIEWS", "0"))
+PATCH = tuple(int(x) for x in os.environ.get("PASS_PATCH", "11,2").split(","))
 dev = torch.device("cuda", 0)
 
 
@@ -36,20 +44,26 @@ def main():
     geom = default_params()
     geom.max_iterations = ITERS
     geom.geom_consistency = 1
+    for p in (photo, geom):
+        p.patch_size, p.radius_increment = PATCH
     planes = [torch.empty((H, W, 4), dtype=torch.float32, device=dev) for _ in range(V)]
     costs = [torch.empty((H, W), dtype=torch.float32, device=dev) for _ in range(V)]
     depth = [torch.empty((H, W), dtype=torch.float32, device=dev) for _ in range(V)]
     ids = {v: [v] + list(setup.pairs[v][:NSRC]) for v in range(V)}
-    out = {"W": W, "H": H, "nsrc": NSRC, "iters": ITERS, "photometric_ms": [], "geometric_ms": []}
+    views = range(min(VIEWS, V)) if VIEWS else range(V)
+    out = {"W": W, "H": H, "nsrc": NSRC, "iters": ITERS, "patch_size": PATCH[0], "radius_increment": PATCH[1],
+           "timed_views": len(views),
+           "general_kernels": PATCH != (11, 2) or os.environ.get("ACMMP_GENERAL_PATCH", "")[:1] == "1",
+           "photometric_ms": [], "geometric_ms": []}
     for rep in range(REPS + 1):
         pool.reset_timing()
-        for v in range(V):  # the photometric pass of the cfg2 step: every view's depth
+        for v in (views if rep else range(V)):  # the photometric pass of the cfg2 step: every view's depth
             photometric_view(pool, eng, photo, [cams[i] for i in ids[v]], [imgs[i].data_ptr() for i in ids[v]],
                              planes[v].data_ptr(), costs[v].data_ptr(), depth[v].data_ptr())
         torch.cuda.synchronize()
         p_ms = pool.sweep_ms / max(pool.sweep_launches, 1)
         pool.reset_timing()
-        for v in range(V):
+        for v in views:
             geometric_view(pool, eng, geom, [cams[i] for i in ids[v]], [imgs[i].data_ptr() for i in ids[v]],
                            [depth[i].data_ptr() for i in ids[v]], planes[v].data_ptr(), costs[v].data_ptr())
         torch.cuda.synchronize()
