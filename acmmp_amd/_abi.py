@@ -188,6 +188,9 @@ SIGNATURES = {
     "acmmp_set_hierarchy_inputs": (C.c_int, [_CTX, _FP, C.c_int, C.c_int, _FP]),
     "acmmp_set_hierarchy_inputs_device": (C.c_int, [_CTX, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "acmmp_set_seed_prior": (C.c_int, [_CTX, _FP]),
+    "acmmp_set_seed_prior_device": (C.c_int, [_CTX, C.c_void_p]),
+    "acmmp_seed_planes_device": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                           C.c_int, C.POINTER(Camera), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "acmmp_set_planar_prior": (C.c_int, [_CTX, _FP, C.c_int, _U32P]),
     "acmmp_get_support_points": (C.c_int, [_CTX, _I32P, C.c_int, C.POINTER(C.c_int)]),
     "acmmp_delaunay_triangulation": (C.c_int, [C.c_int, C.c_int, _I32P, C.c_int, _I32P, C.c_int,

@@ -977,6 +977,29 @@ int acmmp_set_seed_prior(acmmp_ctx *ctx, const float *planes4) {
     return ACMMP_OK;
 }
 
+int acmmp_set_seed_prior_device(acmmp_ctx *ctx, const float *d_planes4) {
+    int rc = check_ready(ctx);
+    if (rc) return rc;
+    if (!d_planes4) return set_err(ctx, ACMMP_ERR_ARG, "planes NULL");
+    const size_t P = (size_t)ctx->W * ctx->H;
+    // the seed buffer lives as long as the view size (free_state): kept, so a
+    // queued run that still reads it is simply ordered before this copy
+    if (!ctx->d_seed) HIP_TRY(ctx, dalloc(ctx->d_seed, P));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_seed, d_planes4, P * sizeof(float4), hipMemcpyDeviceToDevice, ctx->stream));
+    ctx->prm.seeded = 1;
+    ctx->have_seed = true;
+    return ACMMP_OK;
+}
+
+int acmmp_internal_launch_seed_planes(int device, const uint16_t *d_depth, int dw, int dc, const uint16_t *d_normals,
+                                      int nw, int scale, const acmmp_camera *cam, int rows, int cols,
+                                      float *d_planes4, void *stream) {
+    HIP_TRY(nullptr, hipSetDevice(device));
+    HIP_TRY(nullptr, launch_seed_planes(d_depth, dw, dc, d_normals, nw, scale, *cam, rows, cols,
+                                        reinterpret_cast<float4 *>(d_planes4), (hipStream_t)stream));
+    return ACMMP_OK;
+}
+
 int acmmp_set_planar_prior(acmmp_ctx *ctx, const float *plane_params4, int num_planes, const uint32_t *mask) {
     int rc = check_ready(ctx);
     if (rc) return rc;

@@ -129,6 +129,10 @@ hipError_t launch_pad_h16(const float *src, int spitch, int W, int H, void *dst,
 hipError_t launch_pad_quad(const float *src, int spitch, int W, int H, uint32_t *dst, int dpitch,
                            uint32_t *not_u8, hipStream_t stream);
 hipError_t launch_depth_planes(const float *depth, size_t n, float4 *out, hipStream_t stream);
+// Seeded planes of a rows x cols view from decoded prior maps (k_seed_planes):
+// pixel (i, j) samples (i * scale, j * scale). No bounds are checked here.
+hipError_t launch_seed_planes(const uint16_t *depth, int dw, int dc, const uint16_t *normals, int nw, int scale,
+                              const acmmp_camera &cam, int rows, int cols, float4 *out, hipStream_t stream);
 hipError_t launch_jbu(const float *img, int W, int H, const float *depth, int sw, int sh, int image_scale,
                       float *out, hipStream_t stream);
 hipError_t launch_selftest_rcp(unsigned long long *mismatch, unsigned long long *checked, hipStream_t s);

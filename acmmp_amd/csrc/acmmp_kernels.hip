@@ -249,6 +249,61 @@ hipError_t launch_depth_planes(const float *depth, size_t n, float4 *out, hipStr
     return hipGetLastError();
 }
 
+// pSampler::GetPriorPlaneEstimate (src/acmmp_definitions.cpp:99-177): the
+// seeded plane of output pixel (i, j) of a rows x cols view from the decoded
+// 16-bit prior maps, one thread per pixel. The host loop of
+// acmmp_prior_plane_estimate (acmmp_pipeline.cpp) restated: every operation a
+// separate IEEE fp32 operation in the host's order (this unit builds with
+// -ffp-contract=off; `/` and the square root are correctly rounded), so the
+// planes are the host's bit for bit. The depth word is read at r*dw*dc + c
+// (Mat_<float>::at(r, c) on a possibly multi-channel map), the normal words in
+// B, G, R order as stored, and normVec3 multiplies by the norm: all kept.
+// The launcher's caller has checked that the largest indices are in range.
+__global__ __launch_bounds__(256) void k_seed_planes(const uint16_t *__restrict__ depth, int dw, int dc,
+                                                     const uint16_t *__restrict__ normals, int nw, int scale,
+                                                     acmmp_camera cam, int rows, int cols,
+                                                     float4 *__restrict__ out) {
+    const int j = blockIdx.x * 64 + threadIdx.x;
+    const int i = blockIdx.y * 4 + threadIdx.y;
+    if (j >= cols || i >= rows) return;
+    const size_t r = (size_t)i * (size_t)scale, c = (size_t)j * (size_t)scale;
+    const size_t di = r * (size_t)dw * (size_t)dc + c;
+    const size_t ni = (r * (size_t)nw + c) * 3;
+    // Mat::convertTo(CV_32F, alpha, beta): src * alpha + beta in float
+    const float dist = cam.depth_max - cam.depth_min;
+    const float range = dist / 65535.0f;
+    const float nalpha = (float)(2.0 / 65536.0), nbeta = -1.0f;
+    const float d = (float)depth[di] * range + cam.depth_min;
+    float nx = (float)normals[ni] * nalpha + nbeta;
+    float ny = (float)normals[ni + 1] * nalpha + nbeta;
+    float nz = (float)normals[ni + 2] * nalpha + nbeta;
+    // depth_normal_to_plane (:72-89): getViewDirection, the flip, normVec3, distance_to_origin
+    const float X0 = d * (j - cam.K[2]) / cam.K[0];
+    const float X1 = d * (i - cam.K[5]) / cam.K[4];
+    const float X2 = d;
+    const float norm = dm_sqrt(X0 * X0 + X1 * X1 + X2 * X2);
+    const float v0 = X0 / norm, v1 = X1 / norm, v2 = X2 / norm;
+    const float dot = nx * v0 + ny * v1 + nz * v2;
+    if (dot > 0.0f) {
+        nx = -nx;
+        ny = -ny;
+        nz = -nz;
+    }
+    const float n2 = nx * nx + ny * ny + nz * nz;
+    const float s = dm_sqrt(n2);
+    nx *= s;
+    ny *= s;
+    nz *= s;
+    out[(size_t)i * cols + j] = make_float4(nx, ny, nz, -(nx * X0 + ny * X1 + nz * X2));
+}
+
+hipError_t launch_seed_planes(const uint16_t *depth, int dw, int dc, const uint16_t *normals, int nw, int scale,
+                              const acmmp_camera &cam, int rows, int cols, float4 *out, hipStream_t stream) {
+    dim3 block(64, 4), grid((cols + 63) / 64, (rows + 3) / 4);
+    k_seed_planes<<<grid, block, 0, stream>>>(depth, dw, dc, normals, nw, scale, cam, rows, cols, out);
+    return hipGetLastError();
+}
+
 hipError_t launch_jbu(const float *img, int W, int H, const float *depth, int sw, int sh, int image_scale,
                       float *out, hipStream_t stream) {
     dim3 block(64, 4), grid((W + 63) / 64, (H + 3) / 4);

@@ -28,6 +28,8 @@ void usage() {
         "usage: acmmp_main <dense_folder> [options]\n"
         "  --output_dir NAME        output working directory name (default /ACMMP)\n"
         "  -p, --prior              seed the first pass from <dense>priors/{depths,normals}/NNNNNNNN.png\n"
+        "                           (default output directory /ACMMP_PRIOR); with either pass order and with\n"
+        "                           --view_parallel, where the planes are built on the GPU\n"
         "  --device N               HIP device (default 0)\n"
         "  --iterations N           PatchMatch iterations per run (default: the reference's 2)\n"
         "  --seed N                 base RNG seed (default 1234)\n"
@@ -240,11 +242,8 @@ int main(int argc, char **argv) {
 
     const int geom_iterations = 2;
     if (view_parallel) {
-        if (prior) {
-            std::fprintf(stderr, "acmmp_main: -p is not supported with --view_parallel\n");
-            return 2;
-        }
         VpOptions vo;
+        vo.prior = prior;  // (the priors were found and the folder renamed above, before any device work)
         vo.dense = dense_folder;
         vo.output_dir = output_dir;
         vo.device = device_set ? device : -1;

@@ -221,14 +221,23 @@ int load_view(const std::string &dense, int id, int max_image_size, acmmp::Image
 
 // ---- pSampler (src/acmmp_definitions.cpp:8-177): seeded plane priors from
 // 16-bit PNG depth / normal maps under <dense>priors/{depths,normals}/%08d.png
-// (the reference concatenates "priors" to dense_folder without a separator).
-std::string prior_path(const std::string &dense, const char *kind, int cam) {
-    return dense + "priors/" + kind + "/" + id8(cam) + ".png";
-}
+// (the reference concatenates "priors" to dense_folder without a separator);
+// paths and the loader of a camera's two maps: acmmp_hostio.h.
+using acmmp_hostio::prior_path;
 
 bool read_png(const std::string &path, std::vector<uint16_t> &px, int &w, int &h, int &c) {
     int bit_depth = 0;
     return acmmp_hostio::read_png(path, px, w, h, c, bit_depth) == ACMMP_OK;
+}
+
+// The sample step of GetPriorPlaneEstimate (src/acmmp_definitions.cpp:126)
+// and, in closed form, whether the largest indices the rows x cols loop reads
+// lie inside the maps (the loop's own per-pixel test, at its last pixel).
+bool prior_maps_cover(int dw, int dh, int dc, int nw, int nh, int rows, int cols, int *scale_out) {
+    const int scale = dh / rows;
+    *scale_out = scale;
+    const long long r = (long long)(rows - 1) * scale, c = (long long)(cols - 1) * scale;
+    return r < dh && r < nh && c < nw && r * dw * dc + c < (long long)dw * dh * dc;
 }
 
 // depth_normal_to_plane (:72-89) with getViewDirection, normVec3 (which
@@ -272,12 +281,12 @@ int acmmp_priors_available(const char *dense_folder, int num_cams) {
 int acmmp_prior_plane_estimate(const char *dense_folder, int cam_num, const acmmp_camera *cam, int rows, int cols,
                                float *planes4) {
     if (!dense_folder || !cam || rows <= 0 || cols <= 0 || !planes4) return fail(ACMMP_ERR_ARG, "bad args");
-    std::vector<uint16_t> dpx, npx;
-    int dw, dh, dc, nw, nh, nc;
-    const std::string dp = prior_path(dense_folder, "depths", cam_num), np = prior_path(dense_folder, "normals", cam_num);
-    if (!read_png(dp, dpx, dw, dh, dc) || !read_png(np, npx, nw, nh, nc))
-        return fail(ACMMP_ERR_IO, "failed to load prior images: %d (%s)", cam_num, dp.c_str());
-    if (nc != 3) return fail(ACMMP_ERR_UNSUPPORTED, "prior normal map %s has %d channels", np.c_str(), nc);
+    acmmp_hostio::PriorMaps maps;
+    std::string message;
+    const int lrc = acmmp_hostio::read_prior_maps(dense_folder, cam_num, maps, message);
+    if (lrc) return fail(lrc, "%s", message.c_str());
+    const std::vector<uint16_t> &dpx = maps.depth, &npx = maps.normals;
+    const int dw = maps.dw, dh = maps.dh, dc = maps.dc, nw = maps.nw, nh = maps.nh;
     // Mat::convertTo(CV_32F, alpha, beta): src * alpha + beta in float
     const float dist = cam->depth_max - cam->depth_min;
     const float range = dist / 65535.0f;
@@ -297,6 +306,23 @@ int acmmp_prior_plane_estimate(const char *dense_folder, int cam_num, const acmm
             const float nz = (float)npx[ni + 2] * nalpha + nbeta;
             depth_normal_to_plane(base_d, nx, ny, nz, j, i, *cam, planes4 + ((size_t)i * cols + j) * 4);
         }
+    return ACMMP_OK;
+}
+
+int acmmp_seed_planes_device(int device, const uint16_t *d_depth, int dw, int dh, int dc, const uint16_t *d_normals,
+                             int nw, int nh, const acmmp_camera *cam, int rows, int cols, float *d_planes4,
+                             void *stream) {
+    if (!d_depth || !d_normals || !cam || !d_planes4 || rows <= 0 || cols <= 0 || dw <= 0 || dh <= 0 || dc <= 0 ||
+        nw <= 0 || nh <= 0)
+        return fail(ACMMP_ERR_ARG, "bad args");
+    // every index the kernel forms is at most the one checked here: no
+    // out-of-range read can be launched (scale 0 samples (0, 0) everywhere)
+    int scale = 0;
+    if (!prior_maps_cover(dw, dh, dc, nw, nh, rows, cols, &scale))
+        return fail(ACMMP_ERR_ARG, "prior maps %dx%d smaller than %dx%d", dw, dh, cols, rows);
+    const int rc = acmmp_internal_launch_seed_planes(device, d_depth, dw, dc, d_normals, nw, scale, cam, rows, cols,
+                                                     d_planes4, stream);
+    if (rc) return fail(rc, "seed plane kernel launch failed on device %d", device);
     return ACMMP_OK;
 }
 

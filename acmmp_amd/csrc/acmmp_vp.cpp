@@ -9,7 +9,10 @@
 //   * per scale (src/main_ACMMP.cpp:96-176): the images every owned view
 //     needs are decoded once (acmmp_load_view) and kept in HBM; the first
 //     scale runs the photometric + planar-prior pass, finer scales JBU +
-//     the hierarchy pass; then two geometric passes;
+//     the hierarchy pass; then two geometric passes; with -p the first
+//     pass of the first scale is seeded from the prior PNGs (pSampler,
+//     src/acmmp_definitions.cpp:99-177): the decoded 16-bit maps are uploaded
+//     and the planes built on the device (acmmp_seed_planes_device);
 //   * per view: the engine borrows the resident images
 //     (acmmp_set_images_device), the gathered depth maps and the view's
 //     previous state (acmmp_set_depth_maps_device /
@@ -62,6 +65,7 @@
 
 #include "../../include/acmmp.h"
 #include "acmmp_dense.h"
+#include "acmmp_hostio.h"
 #include "acmmp_vp.h"
 #include "acmmp_vp_plan.h"
 
@@ -380,6 +384,7 @@ class PaddedGather {
 // One pass of the schedule over every view (src/main_ACMMP.cpp:96-176)
 struct Pass {
     bool geom, planar, hier, multi;
+    bool seeded = false;  // -p: the first scale's first pass starts from the prior planes (:107-120)
     // the first scale: photometric, then again with the planar prior (:109-120)
     static Pass planar_prior() { return {false, true, false, false}; }
     // a finer scale, after JBU: the same from the upsampled previous scale (:146-155)
@@ -420,7 +425,14 @@ class Driver {
             }
             if (first) {
                 first = false;
-                run_pass(Pass::planar_prior());
+                Pass pass = Pass::planar_prior();
+                if (o_.prior) {
+                    Clock c(this, "prior_load");
+                    load_prior_maps();
+                    pass.seeded = true;
+                }
+                run_pass(pass);
+                prior_maps_.clear();  // only this pass is seeded
             } else {
                 {
                     Clock c(this, "jbu");
@@ -621,6 +633,68 @@ class Driver {
         }
     }
 
+    // -p: the decoded prior maps of every view this rank computes (a band of
+    // a split view needs the view's whole seed: every rank reads it from the
+    // dense folder), PNGs read on the loader pool, words uploaded as they are.
+    // pSampler is asked for camera `problem index` (src/acmmp_definitions.cpp:277).
+    struct PriorMapsDev {
+        DevBuf depth, normals;  // uint16 words (acmmp_hostio::PriorMaps' layout)
+        int dw = 0, dh = 0, dc = 0, nw = 0, nh = 0;
+    };
+    void load_prior_maps() {
+        const std::vector<int> views = computed();
+        std::vector<acmmp_hostio::PriorMaps> host(views.size());
+        std::vector<std::string> msg(views.size());
+        std::string err;
+        const int rc = parallel_index(
+            (int)views.size(), acmmp_host_threads(),
+            [&](int i) {
+                const size_t k = (size_t)i;
+                return acmmp_hostio::read_prior_maps(o_.dense, views[k], host[k], msg[k]);
+            },
+            [&](int i) { return msg[(size_t)i]; }, err);
+        if (rc) fail(err);
+        auto upload = [](const std::vector<uint16_t> &words) {
+            DevBuf d((words.size() + 1) / 2);
+            hip_check(hipMemcpy(d.p, words.data(), words.size() * sizeof(uint16_t), hipMemcpyHostToDevice),
+                      "hipMemcpy");
+            return d;
+        };
+        for (size_t k = 0; k < views.size(); ++k) {
+            const acmmp_hostio::PriorMaps &m = host[k];
+            PriorMapsDev d;
+            d.depth = upload(m.depth);
+            d.normals = upload(m.normals);
+            d.dw = m.dw, d.dh = m.dh, d.dc = m.dc, d.nw = m.nw, d.nh = m.nh;
+            prior_maps_[views[k]] = std::move(d);
+        }
+    }
+
+    // The seeded pass's start planes of view t.view on an engine that holds
+    // its images (GetPriorPlaneEstimate + SetPlanarPrior,
+    // src/acmmp_definitions.cpp:275-281): built on `cs` at the view's size with
+    // GetCamera(problem index) -- an index into the problem's own cameras,
+    // camera 0 beyond them, as the reference -- and copied into the engine's
+    // seed buffer. The engine reads the returned buffer on its stream: kept
+    // until its run has been synchronised.
+    DevBuf set_seed_prior(acmmp_ctx *eng, const Task &t, hipStream_t cs) {
+        const acmmp_problem &pr = problems_[(size_t)t.view];
+        const int k = t.view < 1 + pr.num_src_images ? t.view : 0;
+        const acmmp_camera &cam = cams_.at(k == 0 ? pr.ref_image_id : pr.src_image_ids[k - 1]);
+        const acmmp_camera &ref = ref_cam(t.view);
+        const PriorMapsDev &m = prior_maps_.at(t.view);
+        DevBuf planes((size_t)ref.width * ref.height * 4);
+        const int rc = acmmp_seed_planes_device(o_.device, reinterpret_cast<const uint16_t *>(m.depth.p), m.dw, m.dh,
+                                                m.dc, reinterpret_cast<const uint16_t *>(m.normals.p), m.nw, m.nh, &cam,
+                                                ref.height, ref.width, planes.p, cs);
+        if (rc)
+            fail("view " + std::to_string(pr.ref_image_id) + ": acmmp_seed_planes_device: " +
+                 acmmp_pipeline_last_error());
+        acmmp_check(acmmp_wait_stream(eng, cs), "acmmp_wait_stream", eng);
+        acmmp_check(acmmp_set_seed_prior_device(eng, planes.p), "acmmp_set_seed_prior_device", eng);
+        return planes;
+    }
+
     // height and width of every view at this scale
     void read_shapes() {
         height_.assign(problems_.size(), 0);
@@ -710,8 +784,9 @@ class Driver {
     ViewState compute(acmmp_ctx *eng, const Task &t, hipStream_t cs, Run run) {
         set_view_inputs(eng, t);
         const acmmp_camera &c = ref_cam(t.view);
-        DevBuf scaled;
+        DevBuf scaled, seed;
         if (t.pass.hier) scaled = set_hierarchy_inputs(eng, state_[(size_t)t.view], c.width, c.height, cs);
+        if (t.pass.seeded) seed = set_seed_prior(eng, t, cs);
         ViewState out(c.width, c.height);
         (this->*run)(eng, t.pass, out, cs);
         return out;
@@ -922,6 +997,7 @@ class Driver {
     std::map<int, DevBuf> images_;
     std::map<int, acmmp_texture *> textures_;  // ~ the reference's texture objects, per image and scale
     std::map<int, acmmp_camera> cams_;
+    std::map<int, PriorMapsDev> prior_maps_;  // -p, first pass only: per problem index
     std::vector<int> height_, width_;  // of every view at this scale
     int hmax_ = 0, wmax_ = 0;
     PaddedGather gathered_images_;  // this scale's images of every view (textures borrow it)

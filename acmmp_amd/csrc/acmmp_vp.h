@@ -12,6 +12,7 @@ struct VpOptions {
     int patch_size = 0;               // PatchMatch patch geometry of every run; 0: the defaults 11 / 2
     int radius_increment = 0;
     unsigned seed = 1234;             // RNG key of view v: seed + ref id, pass index
+    bool prior = false;               // -p: seed the first pass from <dense>priors/{depths,normals}/%08d.png
     int geom_iterations = 2;          // geometric passes per scale (src/main_ACMMP.cpp:109)
     int concurrent_views = 2;         // engines (HIP streams) per GPU
     bool exchange_rccl = true;        // RCCL all-gather, else TCP through the rendezvous

@@ -34,7 +34,7 @@ import torch.distributed as dist
 from . import _abi
 from . import io as aio
 from . import pipeline
-from .engine import ACMMP, AcmmpError, joint_bilateral_upsample_device
+from .engine import ACMMP, AcmmpError, joint_bilateral_upsample_device, seed_planes_device
 
 
 def lpt_assign(costs: list, world: int) -> list:
@@ -136,6 +136,7 @@ class ViewTask:
     textures: Optional[list] = None        # engine.Texture per image (prebuilt footprint records)
     patch_size: int = 0                    # patch geometry of the run; 0: the defaults 11 / 2
     radius_increment: int = 0
+    seed_planes: Optional[torch.Tensor] = None  # (H, W, 4) seeded start planes: -p, the first pass only
 
 
 @dataclass
@@ -207,6 +208,8 @@ def engine_setup(t: ViewTask, eng: ACMMP):
     if t.hierarchy:
         scaled, up = t.hier_inputs
         eng.set_hierarchy_inputs_device(scaled.data_ptr(), scaled.shape[1], scaled.shape[0], up.data_ptr())
+    if t.seed_planes is not None:  # SetPlanarPrior (src/acmmp_definitions.cpp:275-281); the task keeps the tensor
+        eng.set_seed_prior_device(t.seed_planes.data_ptr())
 
 
 def _run_ms(eng: ACMMP) -> float:
@@ -238,14 +241,22 @@ class ViewParallelPipeline:
     costs stay on the device between passes, the gathered depth maps are
     borrowed in place, one pool of engines (one HIP stream each) is reused
     for every view and pass, and the .dmb files are written by a writer pool
-    from device-to-host copies while the next pass computes."""
+    from device-to-host copies while the next pass computes.
 
-    def __init__(self, dense_folder: str, output_dir: str = "/ACMMP", device: int = 0, seed: int = 1234,
+    prior=True is main_ACMMP's -p (src/main_ACMMP.cpp:72-90, :107-120): the
+    first pass of the first scale starts from the seeded planes of
+    <dense>priors/{depths,normals}/%08d.png, built on the device from the
+    decoded 16-bit maps; output_dir then defaults to /ACMMP_PRIOR."""
+
+    def __init__(self, dense_folder: str, output_dir: Optional[str] = None, device: int = 0, seed: int = 1234,
                  max_iterations: int = 0, geom_iterations: int = 2, group=None,
                  compute: Optional[Callable] = None, jbu: Optional[Callable] = None, write_outputs: bool = True,
                  comm_device: Optional[torch.device] = None, tensor_device: Optional[torch.device] = None,
                  concurrent_views: int = 2, timing: bool = False, split_tail: bool = True,
-                 patch_size: int = 0, radius_increment: int = 0):
+                 patch_size: int = 0, radius_increment: int = 0, prior: bool = False):
+        self.prior = bool(prior)
+        if output_dir is None:
+            output_dir = "/ACMMP_PRIOR" if prior else "/ACMMP"
         self.patch_size = patch_size
         self.radius_increment = radius_increment
         self.dense = dense_folder
@@ -284,6 +295,9 @@ class ViewParallelPipeline:
         self.problems = pipeline.generate_sample_list(dense_folder)
         self.index_of = {p.ref_image_id: i for i, p in enumerate(self.problems)}
         self.max_num_downscale = pipeline.compute_multiscale_settings(dense_folder, self.problems)
+        if prior and not pipeline.priors_available(dense_folder, len(self.problems)):
+            raise AcmmpError("Initialisation from a prior was requested, but no suitable priors were found.")
+        self.seed_planes = {}  # -p, first pass only: problem index -> (H, W, 4) tensor
         costs = []
         for p in self.problems:
             w, h = aio.view_size(dense_folder, p.ref_image_id)
@@ -360,6 +374,48 @@ class ViewParallelPipeline:
             from .engine import Texture
             self.textures = {i: Texture.of(im, self.device) for i, im in self.images.items()}
 
+    def _load_seed_planes(self):
+        """-p: the seeded start planes of every view this rank computes, at
+        the first scale's size (pSampler::GetPriorPlaneEstimate,
+        src/acmmp_definitions.cpp:99-177, :275-281). pSampler is asked for
+        camera `problem index`, and GetCamera(problem index) indexes the
+        problem's own cameras (reference first, then sources; camera 0 beyond
+        them): both kept. Every rank with a band of a split view builds the
+        view's whole seed from the dense folder. The PNGs are read on a thread
+        pool, their 16-bit words uploaded and the planes built by the kernel
+        on torch's stream (the engines order their copy after it); on CPU
+        tensors (injected stand-in engines) the host estimate fills them."""
+        views = self.mine + self.split
+        shapes = self._shapes()
+
+        def camera(v):
+            p = self.problems[v]
+            ids = [p.ref_image_id] + p.sources
+            return self.cams[ids[v] if v < len(ids) else ids[0]]
+
+        if self.tdev.type != "cuda":
+            for v in views:
+                H, W = shapes[v]
+                self.seed_planes[v] = torch.from_numpy(pipeline.prior_plane_estimate(self.dense, v, camera(v), H, W))
+            return
+        from concurrent.futures import ThreadPoolExecutor
+        lib = _abi.load_library()
+        with ThreadPoolExecutor(max_workers=max(1, min(lib.acmmp_host_threads(), len(views) or 1))) as ex:
+            maps = list(ex.map(lambda v: pipeline.read_prior_maps(self.dense, v), views))
+        stream = torch.cuda.current_stream(self.tdev).cuda_stream
+        for v, (depth, normals) in zip(views, maps):
+            H, W = shapes[v]
+            # (torch has no arithmetic on uint16: the words travel as int16 bit patterns)
+            d = torch.from_numpy(np.ascontiguousarray(depth).view(np.int16)).to(self.tdev)
+            n = torch.from_numpy(np.ascontiguousarray(normals).view(np.int16)).to(self.tdev)
+            out = torch.empty((H, W, 4), dtype=torch.float32, device=self.tdev)
+            dh, dw = depth.shape[:2]
+            seed_planes_device(d.data_ptr(), dw, dh, 1 if depth.ndim == 2 else depth.shape[2], n.data_ptr(),
+                               normals.shape[1], normals.shape[0], camera(v), H, W, out.data_ptr(), self.device,
+                               stream)
+            self.seed_planes[v] = out
+        self._sync()  # the uploaded words are released here
+
     def _check_split(self):
         """A view is split only if every band holds the 23-row halo at the
         coarsest scale (this first load's shapes; later scales are larger);
@@ -400,7 +456,7 @@ class ViewParallelPipeline:
                 e.timing_on = self.timing
         return self.pool.map(lambda eng, t: self.compute(t, eng), tasks)
 
-    def _task(self, v: int, geom: bool, planar: bool, hierarchy: bool, multi: bool) -> ViewTask:
+    def _task(self, v: int, geom: bool, planar: bool, hierarchy: bool, multi: bool, seeded: bool = False) -> ViewTask:
         p = self.problems[v]
         ids = [p.ref_image_id] + p.sources
         t = ViewTask(index=v, ref_id=p.ref_image_id, ids=ids, cams=[self.cams[i] for i in ids],
@@ -409,7 +465,7 @@ class ViewParallelPipeline:
                      geom=geom, planar=planar, hierarchy=hierarchy,
                      multi=multi, seed_lo=self.seed + p.ref_image_id, seed_hi=self.pass_index,
                      max_iterations=self.max_iterations, patch_size=self.patch_size,
-                     radius_increment=self.radius_increment)
+                     radius_increment=self.radius_increment, seed_planes=self.seed_planes[v] if seeded else None)
         if geom:
             t.depths = [self.depths[self.index_of[i]] for i in ids]
             prev = self.state[v]
@@ -443,8 +499,9 @@ class ViewParallelPipeline:
                                   planar_prior=t.planar)
         return ViewResult(planes, costs, {})
 
-    def run_pass(self, geom: bool, planar: bool, hierarchy: bool, multi: bool, exchange: DepthExchange):
-        tasks = [self._task(v, geom, planar, hierarchy, multi) for v in self.mine]
+    def run_pass(self, geom: bool, planar: bool, hierarchy: bool, multi: bool, exchange: DepthExchange,
+                 seeded: bool = False):
+        tasks = [self._task(v, geom, planar, hierarchy, multi, seeded) for v in self.mine]
         t0 = time.perf_counter()
         with self._timed("compute"):
             self._sync()
@@ -461,7 +518,7 @@ class ViewParallelPipeline:
         # the tail views, every rank on a band of each
         for v in self.split:
             with self._timed("split_compute"):
-                t = self._task(v, geom, planar, hierarchy, multi)
+                t = self._task(v, geom, planar, hierarchy, multi, seeded)
                 self._sync()
                 res = self._run_split(t)
             self.state[v] = res
@@ -533,7 +590,11 @@ class ViewParallelPipeline:
                                          out_device=self.tdev)
                 if first:
                     first = False
-                    self.run_pass(False, True, False, False, exchange)
+                    if self.prior:
+                        with self._timed("seed_planes"):
+                            self._load_seed_planes()
+                    self.run_pass(False, True, False, False, exchange, seeded=self.prior)
+                    self.seed_planes = {}  # only this pass is seeded
                 else:
                     with self._timed("jbu"):
                         for v in self.mine + self.split:  # JointBilateralUpsampling, resident (split: on every rank)
@@ -567,7 +628,9 @@ def main():
     import argparse
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("dense_folder")
-    ap.add_argument("--output_dir", default="/ACMMP")
+    ap.add_argument("--output_dir", default=None, help="default /ACMMP, with -p /ACMMP_PRIOR")
+    ap.add_argument("-p", "--prior", action="store_true",
+                    help="seed the first pass from <dense>priors/{depths,normals}/NNNNNNNN.png")
     ap.add_argument("--iterations", type=int, default=0)
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--patch_size", type=int, default=0, help="PatchMatch patch size (default 11)")
@@ -585,7 +648,7 @@ def main():
         dist.init_process_group(backend)
     pipe = ViewParallelPipeline(args.dense_folder, args.output_dir, device=local_rank, seed=args.seed,
                                 max_iterations=args.iterations, concurrent_views=args.concurrent_views,
-                                patch_size=args.patch_size, radius_increment=args.radius_increment)
+                                patch_size=args.patch_size, radius_increment=args.radius_increment, prior=args.prior)
     out = pipe.run()
     if pipe.rank == 0:
         print(f"Depth/normal/cost maps written under {out}")

@@ -95,6 +95,26 @@ def joint_bilateral_upsample_device(d_image: int, width: int, height: int, d_dep
     return isc.value
 
 
+def seed_planes_device(d_depth: int, dw: int, dh: int, dc: int, d_normals: int, nw: int, nh: int, cam: _abi.Camera,
+                       rows: int, cols: int, d_planes: int, device: int = 0, stream: int | None = None) -> None:
+    """pSampler::GetPriorPlaneEstimate's plane conversion
+    (src/acmmp_definitions.cpp:99-177) on the GPU (acmmp_seed_planes_device):
+    from a camera's decoded uint16 prior maps in device memory (depth dh x dw
+    x dc, normals nh x nw x 3 in B, G, R order) to rows x cols float4 planes at
+    d_planes, one kernel enqueued on `stream` (a hipStream_t; None/0 = the
+    legacy default stream). Bit-identical to pipeline.prior_plane_estimate;
+    maps too small for rows x cols raise its error and launch nothing."""
+    lib = _abi.load_library()
+    rc = lib.acmmp_seed_planes_device(int(device), C.c_void_p(int(d_depth)), int(dw), int(dh), int(dc),
+                                      C.c_void_p(int(d_normals)), int(nw), int(nh), C.byref(cam), int(rows),
+                                      int(cols), C.c_void_p(int(d_planes)), C.c_void_p(int(stream or 0) or None))
+    if rc != 0:
+        err = AcmmpError(f"acmmp_seed_planes_device failed (status {rc}): "
+                         f"{lib.acmmp_pipeline_last_error().decode(errors='replace')}")
+        err.status = rc
+        raise err
+
+
 class Texture:
     """~ a CUDA texture object (src/ACMMP.cpp:640-662): the padded footprint
     records of one device-resident image, built once and borrowed by every
@@ -341,6 +361,16 @@ class ACMMP:
         """Seeded plane priors (src/ACMMP.cpp:476-523); sets params.seeded."""
         pr = np.ascontiguousarray(prior, dtype=np.float32)
         self._check(self._lib.acmmp_set_seed_prior(self._ctx, _fptr(pr)), "SetPlanarPrior")
+
+    def set_seed_prior_device(self, d_planes: int):
+        """SetPlanarPrior from a device buffer of H x W float4 (e.g. the
+        planes seed_planes_device built): copied on the engine stream after
+        the producer's writes (acmmp_wait_stream), no host wait; sets
+        params.seeded. The buffer must stay valid until the engine stream
+        has passed the copy (synchronize(), or the next run's end)."""
+        self._after_producer()
+        self._check(self._lib.acmmp_set_seed_prior_device(self._ctx, C.c_void_p(int(d_planes))),
+                    "acmmp_set_seed_prior_device")
 
     def CudaPlanarPriorInitialization(self, plane_params: np.ndarray, mask: np.ndarray):
         """src/ACMMP.cpp:811-831: triangle planes + per-pixel label mask."""

@@ -72,6 +72,37 @@ def prior_plane_estimate(dense_folder: str, cam_num: int, cam, rows: int, cols: 
     return out
 
 
+def read_prior_maps(dense_folder: str, cam_num: int):
+    """The decoded prior maps of camera `cam_num` (GetPriorPlaneEstimate's
+    inputs, src/acmmp_definitions.cpp:99-124) through acmmp_read_png:
+    (depth, normals) uint16 arrays, depth (dh, dw) or (dh, dw, dc), normals
+    (nh, nw, 3) in B, G, R order. Errors as prior_plane_estimate reports
+    them."""
+    import numpy as np
+    lib = _abi.load_library()
+    u16 = C.POINTER(C.c_uint16)
+
+    def read(path):
+        w, h, c, bd = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        rc = lib.acmmp_read_png(path.encode(), None, 0, C.byref(w), C.byref(h), C.byref(c), C.byref(bd))
+        if rc != _abi.ERR_ARG:  # the size query of a readable PNG answers ERR_ARG: no buffer
+            return None
+        out = np.empty((h.value, w.value, c.value), dtype=np.uint16)
+        rc = lib.acmmp_read_png(path.encode(), out.ctypes.data_as(u16), out.size, C.byref(w), C.byref(h), C.byref(c),
+                                C.byref(bd))
+        return out if rc == 0 else None
+
+    dp, npth = (f"{dense_folder}priors/{kind}/{cam_num:08d}.png" for kind in ("depths", "normals"))
+    depth, normals = read(dp), read(npth)
+    if depth is None or normals is None:
+        raise AcmmpError(f"GetPriorPlaneEstimate failed (status {_abi.ERR_IO}): "
+                         f"failed to load prior images: {cam_num} ({dp})")
+    if normals.shape[2] != 3:
+        raise AcmmpError(f"GetPriorPlaneEstimate failed (status {_abi.ERR_UNSUPPORTED}): "
+                         f"prior normal map {npth} has {normals.shape[2]} channels")
+    return (depth[..., 0] if depth.shape[2] == 1 else depth), normals
+
+
 def pass_options(geom_consistency=False, planar_prior=False, hierarchy=False, multi_geometry=False,
                  device=0, max_iterations=0, seed_lo=1234, seed_hi=0, write_triangulation=True,
                  verbose=False, seeded=False, patch_size=0, radius_increment=0) -> _abi.PassOptions:

@@ -252,6 +252,13 @@ int acmmp_set_hierarchy_inputs_device(acmmp_ctx *ctx, const float *d_scaled_plan
  * plane priors, float4 per ref pixel (camera-frame normal, distance). Sets
  * params.seeded. */
 int acmmp_set_seed_prior(acmmp_ctx *ctx, const float *planes4);
+/* Same from a device buffer (src/ACMMP.cpp:476-523; e.g. the planes
+ * acmmp_seed_planes_device built): copied device-to-device into the engine's
+ * seed buffer on the engine stream, no host synchronisation. Sets
+ * params.seeded. As for every *_device setter, a producer on another stream
+ * is ordered first with acmmp_wait_stream, and the caller's buffer stays
+ * unchanged until the engine stream has passed the copy. */
+int acmmp_set_seed_prior_device(acmmp_ctx *ctx, const float *d_planes4);
 
 /* ~ ACMMP::CudaPlanarPriorInitialization(vector<float4>, Mat_<float> mask)
  * (src/ACMMP.cpp:811-831): triangle planes (float4 each) and the per-pixel
@@ -472,6 +479,20 @@ int acmmp_priors_available(const char *dense_folder, int num_cams);
  * multiplication by the norm. float4 per pixel, row-major. */
 int acmmp_prior_plane_estimate(const char *dense_folder, int cam_num, const acmmp_camera *cam, int rows, int cols,
                                float *planes4);
+/* The plane conversion of pSampler::GetPriorPlaneEstimate
+ * (src/acmmp_definitions.cpp:99-177) on `device`: from the decoded maps of a
+ * camera already in device memory (d_depth: dh x dw x dc words as
+ * acmmp_read_png returns them, d_normals: nh x nw x 3 words in B, G, R
+ * order) into d_planes4 (rows x cols float4), one kernel enqueued on `stream`
+ * (a hipStream_t; NULL = the legacy default stream), no host synchronisation.
+ * The planes are acmmp_prior_plane_estimate's bit for bit. The largest
+ * indices the rows x cols loop reads (sample step dh / rows, which may be 0:
+ * every pixel then reads (0, 0)) are checked on the host first: maps too
+ * small return ACMMP_ERR_ARG with acmmp_prior_plane_estimate's message
+ * (acmmp_pipeline_last_error) and launch nothing. */
+int acmmp_seed_planes_device(int device, const uint16_t *d_depth, int dw, int dh, int dc, const uint16_t *d_normals,
+                             int nw, int nh, const acmmp_camera *cam, int rows, int cols, float *d_planes4,
+                             void *stream);
 
 /* ~ RunFusion (src/acmmp_definitions.cpp:828-1043): fuse the depth_geom (or
  * depth) + normal maps of all problems into <output>/ACMMP_model.ply (binary

@@ -93,6 +93,10 @@ class ACMMP {
     void SetPlanarPrior(const std::vector<Float4> &prior) {
         check(acmmp_set_seed_prior(ctx_, &prior[0].x), "SetPlanarPrior");
     }
+    // the same from a device buffer of width * height float4 (acmmp_seed_planes_device builds one)
+    void SetPlanarPriorDevice(const float *d_prior4) {
+        check(acmmp_set_seed_prior_device(ctx_, d_prior4), "SetPlanarPriorDevice");
+    }
 
     // ---- run (src/ACMMP.cu:1378-1456)
     void RunPatchMatch() {
