@@ -233,6 +233,9 @@ SIGNATURES = {
     "acmmp_patch_geometry_supported": (C.c_int, [C.c_int, C.c_int]),
     "acmmp_run_fusion": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(Problem), C.c_int, C.c_int, C.c_float, C.c_int,
                                    C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_int)]),
+    "acmmp_run_fusion_jacobi": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(Problem), C.c_int, C.c_int, C.c_float,
+                                          C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_int)]),
+    "acmmp_fusion_jacobi_scan_chunk": (C.c_int, []),
     "acmmp_fusion_last_error": (C.c_char_p, []),
     "acmmp_run_prior_aware_fusion": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(Problem), C.c_int,
                                                C.c_int, C.c_float, C.c_int, C.c_int, C.POINTER(C.c_int)]),

@@ -1,0 +1,443 @@
+// acmmp_fusion_dev.hip — RunFusion (src/acmmp_definitions.cpp:828-1043) in Jacobi order on the
+// device: acmmp_run_fusion_jacobi. The literal fusion (acmmp_fusion.cpp) walks a view's pixels one
+// after the other because an approval masks source pixels that later pixels of the SAME view then
+// skip. Here every pixel of view i reads the masks as they stood before view i's first pixel (its
+// own mask bit and every source's, also when a view lists itself as a source); view i's mask writes
+// become visible to view i + 1. Nothing else changes: view order, pixel order, the float
+// expressions (world_point / project of acmmp_fusion_host.h, shared with the host), the thresholds,
+// and used_list, which the reference never resets between pixels. A view is then three
+// data-parallel steps on one stream:
+//   k_fusion_test    a thread a pixel: per source slot the reference's tests against the masks as
+//                    they stand (nothing writes them meanwhile); out: the pixel's 32-bit hit mask
+//                    (bit j = source slot j passed) and its approval flag
+//   k_fusion_chunks  per chunk of kScanChunk pixels and slot: the chunk's last hit; per chunk: its
+//   k_fusion_carry   approvals. Then across chunks: the last hit before each chunk per slot, and
+//                    the exclusive prefix of the approvals (the points' positions)
+//   k_fusion_apply   a block a chunk: an approved pixel writes its point at its position and, per
+//                    slot, sets the mask bit of the target of the last hit at or before it (that is
+//                    used_list: an unapproved pixel's hit is applied by the next approval unless a
+//                    later hit on the same slot replaced it). Targets are not stored: recomputed by
+//                    the expression the test used. Atomic ORs of single bits: any thread order
+//                    gives the same masks.
+// libm: acos / exp are the project's pinned dm_acosf / dm_expf (the literal fusion calls the
+// host's libm): same bits on host, device and in the tests' restatement. dm_acosf is NaN outside
+// [-1, 1], so GetAngle's "NaN -> 0" gives angle 0 for a dot product just above 1.
+// int(p + 0.5f): the host's conversion of a NaN, an infinity or a value outside int is INT_MIN,
+// which the bounds test rejects; the device's saturates (NaN -> 0, in bounds). src_pixel tests the
+// range before converting: not finite or outside [-2^31, 2^31) is out of bounds.
+#include <hip/hip_runtime.h>
+
+#include "acmmp_fusion_host.h"
+#include "../../include/acmmp_detmath.h"
+
+namespace {
+
+using namespace acmmp_fusion_host;
+
+constexpr int kScanChunk = 1024;  // pixels a scan chunk = threads of an apply block
+constexpr int kMaxSrc = 32;       // source slots: bits of a hit mask
+constexpr int kCarrySeg = 16;     // k_fusion_carry: segments of chunks a row is scanned in
+
+struct DevView {
+    acmmp_camera cam;      // at the maps' size
+    int W, H, nsrc;
+    int src[kMaxSrc];      // [slot j]: the source's view index
+    const float *depth;    // H x W
+    const float *normal;   // H x W x 3
+    uint32_t *mask;        // bit k & 31 of word k >> 5 (MaskBits' 64-bit words, little-endian)
+};
+
+struct DevPoint {  // an approved pixel: its world point and pixel index (normal, colour: the host's)
+    float x, y, z;
+    uint32_t q;
+};
+
+__device__ inline bool mask_bit(const uint32_t *m, int k) { return (m[k >> 5] >> (k & 31)) & 1u; }
+
+// int(p + 0.5f) inside [0, n), with the host's outcome for what int() cannot hold (see the top)
+__device__ inline bool pixel_coord(float p, int n, int &out) {
+    const float v = p + 0.5f;
+    if (!(v >= -2147483648.0f && v < 2147483648.0f)) return false;  // NaN, +-inf, outside int
+    out = (int)v;
+    return out >= 0 && out < n;
+}
+
+// the pixel of source `vs` that world point X falls on; false: outside the source's maps
+__device__ inline bool src_pixel(const F3 &X, const DevView &vs, int &sc, int &sr) {
+    float px, py, proj_depth;
+    project(X, vs.cam, px, py, proj_depth);
+    const bool in_r = pixel_coord(py, vs.H, sr), in_c = pixel_coord(px, vs.W, sc);
+    return in_r && in_c;
+}
+
+__device__ inline float get_angle(const float *a, const float *b) {  // GetAngle
+    const float dot = a[0] * b[0] + a[1] * b[1] + a[2] * b[2];
+    const float angle = dm_acosf(dot);
+    if (angle != angle) return 0.0f;
+    return angle;
+}
+
+__global__ void __launch_bounds__(256)
+k_fusion_test(const DevView *__restrict__ views, int i, int con_num_thresh, float consistency_scalar,
+              uint32_t *__restrict__ hit, uint8_t *__restrict__ approved) {
+    const DevView &vi = views[i];
+    const int N = vi.W * vi.H;
+    const int q = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (q >= N) return;
+    uint32_t hits = 0;
+    bool ok = false;
+    const float ref_depth = vi.depth[q];
+    if (!mask_bit(vi.mask, q) && !(ref_depth <= 0.0f || ref_depth >= vi.cam.depth_max)) {
+        const int r = q / vi.W, c = q - r * vi.W;
+        const F3 X = world_point(c, r, ref_depth, vi.cam);
+        int num_consistent = 0;
+        float dynamic_consistency = 0;
+        for (int j = 0; j < vi.nsrc; ++j) {
+            const DevView &vs = views[vi.src[j]];
+            int sc, sr;
+            if (!src_pixel(X, vs, sc, sr)) continue;
+            const int sp = sr * vs.W + sc;
+            if (mask_bit(vs.mask, sp)) continue;
+            const float src_depth = vs.depth[sp];
+            if (src_depth <= 0.0f) continue;
+            const F3 tmp_X = world_point(sc, sr, src_depth, vs.cam);
+            float tx, ty, proj_depth;
+            project(tmp_X, vi.cam, tx, ty, proj_depth);
+            // as stage_reproject (acmmp_fusion.cpp): std::pow(v, 2) of a float is exact in double
+            const double dx = (double)(c - tx), dy = (double)(r - ty);
+            const float reproj_error = (float)sqrt(dx * dx + dy * dy);
+            const float relative_depth_diff = fabsf(proj_depth - ref_depth) / ref_depth;
+            if (!(reproj_error < 2.0f && relative_depth_diff < 0.01f)) continue;
+            const float angle = get_angle(&vi.normal[(size_t)q * 3], &vs.normal[(size_t)sp * 3]);
+            if (angle < 0.174533f) {
+                const float tmp_index = reproj_error + 200 * relative_depth_diff + angle * 10;
+                hits |= 1u << j;
+                dynamic_consistency += dm_expf(-tmp_index);
+                num_consistent++;
+            }
+        }
+        ok = num_consistent >= con_num_thresh && (dynamic_consistency > consistency_scalar * num_consistent);
+    }
+    hit[q] = hits;
+    approved[q] = ok ? 1 : 0;
+}
+
+// 32 threads a chunk: thread j finds the chunk's last hit on slot j (-1: none; walks back from the
+// chunk's end, so it stops early where hits are dense), and together they count its approvals.
+__global__ void __launch_bounds__(256)
+k_fusion_chunks(const uint32_t *__restrict__ hit, const uint8_t *__restrict__ approved, int N, int nchunks,
+                int *__restrict__ chunk_last, int *__restrict__ chunk_count) {
+    const int t = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    const int chunk = t >> 5, j = t & 31;
+    if (chunk >= nchunks) return;  // (all 32 threads of a chunk leave together)
+    const int b = chunk * kScanChunk, e = min(N, b + kScanChunk);
+    int last = -1;
+    for (int p = e - 1; p >= b; --p)
+        if ((hit[p] >> j) & 1u) {
+            last = p;
+            break;
+        }
+    chunk_last[chunk * kMaxSrc + j] = last;
+    int cnt = 0;
+    for (int p = b + j; p < e; p += 32) cnt += approved[p];
+    for (int o = 16; o > 0; o >>= 1) cnt += __shfl_down(cnt, o, 32);
+    if (j == 0) chunk_count[chunk] = cnt;
+}
+
+// One block. Rows 0..31: per slot the exclusive running maximum of chunk_last over the chunks (the
+// last hit before the chunk; pixel indices grow with the chunk, -1 = none). Row 32: the exclusive
+// prefix sum of chunk_count, and the view's number of points. A row is scanned in kCarrySeg
+// segments: each thread reduces its segment, then rescans it from what the segments before it hold.
+constexpr int kCarryThreads = (kMaxSrc + 1) * kCarrySeg;
+
+__global__ void __launch_bounds__(576)
+k_fusion_carry(int nchunks, const int *__restrict__ chunk_last, const int *__restrict__ chunk_count,
+               int *__restrict__ carry_last, int *__restrict__ chunk_base, int *__restrict__ view_points) {
+    __shared__ int seg_val[kMaxSrc + 1][kCarrySeg];
+    const int tid = (int)threadIdx.x;
+    const bool active = tid < kCarryThreads, counts = tid >= kMaxSrc * kCarrySeg;
+    const int row = counts ? kMaxSrc : tid & (kMaxSrc - 1);
+    const int seg = counts ? tid - kMaxSrc * kCarrySeg : tid >> 5;
+    const int per = (nchunks + kCarrySeg - 1) / kCarrySeg;
+    const int b = min(nchunks, seg * per), e = min(nchunks, b + per);
+    if (active) {
+        int acc = counts ? 0 : -1;
+        for (int c = b; c < e; ++c) acc = counts ? acc + chunk_count[c] : max(acc, chunk_last[c * kMaxSrc + row]);
+        seg_val[row][seg] = acc;
+    }
+    __syncthreads();
+    if (!active) return;
+    int run = counts ? 0 : -1;
+    for (int s = 0; s < seg; ++s) run = counts ? run + seg_val[row][s] : max(run, seg_val[row][s]);
+    for (int c = b; c < e; ++c) {
+        if (counts) {
+            chunk_base[c] = run;
+            run += chunk_count[c];
+        } else {
+            carry_last[c * kMaxSrc + row] = run;
+            run = max(run, chunk_last[c * kMaxSrc + row]);
+        }
+    }
+    if (counts && seg == kCarrySeg - 1) *view_points = run;  // (the last segment ends at nchunks)
+}
+
+// sets the mask bit of the pixel of source slot j that pixel p of view i falls on
+__device__ inline void set_target(const DevView *views, const DevView &vi, int p, int j) {
+    const int r = p / vi.W, c = p - r * vi.W;
+    const F3 X = world_point(c, r, vi.depth[p], vi.cam);
+    const DevView &vs = views[vi.src[j]];
+    int sc, sr;
+    if (!src_pixel(X, vs, sc, sr)) return;  // (a hit passed this very test in k_fusion_test)
+    const int sp = sr * vs.W + sc;
+    atomicOr(&vs.mask[sp >> 5], 1u << (sp & 31));
+}
+
+__global__ void __launch_bounds__(kScanChunk)
+k_fusion_apply(const DevView *__restrict__ views, int i, const uint32_t *__restrict__ hit,
+               const uint8_t *__restrict__ approved, const int *__restrict__ chunk_last,
+               const int *__restrict__ carry_last, const int *__restrict__ chunk_base, DevPoint *__restrict__ out) {
+    __shared__ uint32_t s_hit[kScanChunk];
+    __shared__ int s_wave[kScanChunk / 64];
+    __shared__ uint32_t s_present;  // slots with a hit somewhere in this chunk
+    const DevView &vi = views[i];
+    const int N = vi.W * vi.H;
+    const int chunk = (int)blockIdx.x, tid = (int)threadIdx.x, q = chunk * kScanChunk + tid;
+    const int lane = tid & 63, wave = tid >> 6;
+    const bool ok = q < N && approved[q];
+    s_hit[tid] = q < N ? hit[q] : 0u;
+    const unsigned long long votes = __ballot(ok);
+    if (lane == 0) s_wave[wave] = __popcll(votes);
+    if (wave == 0) {
+        const unsigned long long present = __ballot(lane < kMaxSrc && chunk_last[chunk * kMaxSrc + (lane & 31)] >= 0);
+        if (lane == 0) s_present = (uint32_t)present;
+    }
+    __syncthreads();
+    if (!ok) return;
+    int pos = chunk_base[chunk] + __popcll(votes & ((1ull << lane) - 1ull));
+    for (int w = 0; w < wave; ++w) pos += s_wave[w];
+    const int r = q / vi.W, c = q - r * vi.W;
+    const F3 X = world_point(c, r, vi.depth[q], vi.cam);
+    out[pos] = DevPoint{X.x, X.y, X.z, (uint32_t)q};
+    const uint32_t slots = vi.nsrc >= kMaxSrc ? 0xffffffffu : (1u << vi.nsrc) - 1u;
+    uint32_t need = slots & s_present;
+    for (int p = tid; need && p >= 0; --p) {  // back to the chunk's start: the last hit per slot
+        uint32_t h = s_hit[p] & need;
+        need &= ~h;
+        for (; h; h &= h - 1) set_target(views, vi, chunk * kScanChunk + p, __ffs((int)h) - 1);
+    }
+    for (uint32_t rest = (slots & ~s_present) | need; rest; rest &= rest - 1) {  // from earlier chunks
+        const int j = __ffs((int)rest) - 1;
+        const int p = carry_last[chunk * kMaxSrc + j];
+        if (p >= 0) set_target(views, vi, p, j);
+    }
+}
+
+using Clock = std::chrono::steady_clock;
+double secs(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double>(b - a).count(); }
+
+// what the call holds on the device and in pinned host memory: released on every way out
+struct DevHold {
+    std::vector<void *> dev, pinned;
+    hipStream_t stream = nullptr;
+    hipEvent_t copied[2] = {nullptr, nullptr};
+    ~DevHold() {
+        if (stream) (void)hipStreamSynchronize(stream);
+        for (hipEvent_t e : copied)
+            if (e) (void)hipEventDestroy(e);
+        for (void *p : dev) (void)hipFree(p);
+        for (void *p : pinned) (void)hipHostFree(p);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+#define FUSION_HIP_TRY(expr)                                                                               \
+    do {                                                                                                   \
+        const hipError_t e_ = (expr);                                                                      \
+        if (e_ != hipSuccess)                                                                              \
+            return ffail(ACMMP_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+    } while (0)
+
+size_t align256(size_t n) { return (n + 255) / 256 * 256; }
+
+}  // namespace
+
+extern "C" {
+
+int acmmp_fusion_jacobi_scan_chunk(void) { return kScanChunk; }
+
+int acmmp_run_fusion_jacobi(const char *dense_folder, const char *output_folder, const acmmp_problem *problems,
+                            int count, int geom_consistency, float consistency_scalar, int con_num_thresh,
+                            const char *image_dir, const char *mask_folder, int device, int *num_points) {
+    if (!dense_folder || !output_folder || !problems || count <= 0) return ffail(ACMMP_ERR_ARG, "bad args");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess) ndev = 0;
+    if (device < 0 || device >= ndev)
+        return ffail(ACMMP_ERR_HIP, "RunFusion in Jacobi order needs a HIP device: device %d of %d asked for", device,
+                     ndev);
+    const std::string dense = dense_folder, out = output_folder;
+    const std::string image_folder = dense + (image_dir ? image_dir : "/images");
+    const bool use_masks = mask_folder && std::string(mask_folder) != " " && mask_folder[0] != 0;
+    const char *suffix = geom_consistency ? "/depths_geom.dmb" : "/depths.dmb";
+    const size_t n = (size_t)count;
+    const bool timing = std::getenv("ACMMP_HOST_TIMING") != nullptr;
+    const auto t_start = Clock::now();
+    Scene sc(problems, n);
+    Pool pool;
+    // the literal fusion's loads, on the pool (acmmp_run_fusion)
+    int rc = pool_for(pool, (int)n, [&](int vi) -> int {
+        const size_t i = (size_t)vi;
+        const int id = problems[i].ref_image_id;
+        const int load_rc = load_view(sc, i, image_folder, dense, result_folder(out, id), suffix);
+        if (load_rc) return load_rc;
+        sc.masks[i].assign((size_t)sc.cols[i] * sc.rows[i]);
+        if (!use_masks) return (int)ACMMP_OK;
+        return load_initial_mask(dense + "/" + mask_folder + "/" + id8(id) + ".png", sc.cols[i], sc.rows[i],
+                                 sc.masks[i]);
+    });
+    if (!rc) rc = resolve_sources(sc);
+    if (rc) return rc;
+    size_t max_pixels = 0;
+    for (size_t i = 0; i < n; ++i) {
+        if ((size_t)sc.cols[i] * sc.rows[i] > (size_t(1) << 27) || problems[i].num_src_images > kMaxSrc)
+            return ffail(ACMMP_ERR_ARG, "view %d: fusion supports images up to 2^27 pixels and 32 sources",
+                         problems[i].ref_image_id);
+        max_pixels = std::max(max_pixels, (size_t)sc.cols[i] * sc.rows[i]);
+    }
+    const auto t_loaded = Clock::now();
+
+    // ---- upload: every view's depth, normal and mask words, and the table of views, once
+    FUSION_HIP_TRY(hipSetDevice(device));
+    DevHold hold;
+    FUSION_HIP_TRY(hipStreamCreateWithFlags(&hold.stream, hipStreamNonBlocking));
+    for (hipEvent_t &e : hold.copied) FUSION_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    auto dev_alloc = [&](size_t bytes, void **p) -> hipError_t {
+        const hipError_t e = hipMalloc(p, std::max(bytes, size_t(256)));
+        if (e == hipSuccess) hold.dev.push_back(*p);
+        return e;
+    };
+    size_t arena_bytes = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const size_t N = (size_t)sc.cols[i] * sc.rows[i];
+        arena_bytes += align256(N * sizeof(float)) + align256(N * 3 * sizeof(float)) +
+                       align256(sc.masks[i].w.size() * sizeof(uint64_t));
+    }
+    char *arena = nullptr;
+    FUSION_HIP_TRY(dev_alloc(arena_bytes, (void **)&arena));
+    std::vector<DevView> views(n);
+    size_t at = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const size_t N = (size_t)sc.cols[i] * sc.rows[i];
+        DevView &v = views[i];
+        v.cam = sc.cameras[i];
+        v.W = sc.cols[i];
+        v.H = sc.rows[i];
+        v.nsrc = problems[i].num_src_images;
+        for (int j = 0; j < kMaxSrc; ++j) v.src[j] = j < v.nsrc ? sc.src_index[i][(size_t)j] : 0;
+        auto put = [&](const void *src, size_t bytes) -> char * {
+            char *d = arena + at;
+            at += align256(bytes);
+            return hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, hold.stream) == hipSuccess ? d : nullptr;
+        };
+        v.depth = (const float *)put(sc.depths[i].data(), N * sizeof(float));
+        v.normal = (const float *)put(sc.normals[i].data(), N * 3 * sizeof(float));
+        v.mask = (uint32_t *)put(sc.masks[i].w.data(), sc.masks[i].w.size() * sizeof(uint64_t));
+        if (!v.depth || !v.normal || !v.mask)
+            return ffail(ACMMP_ERR_HIP, "upload of view %d failed: %s", problems[i].ref_image_id,
+                         hipGetErrorString(hipGetLastError()));
+    }
+    DevView *d_views = nullptr;
+    FUSION_HIP_TRY(dev_alloc(n * sizeof(DevView), (void **)&d_views));
+    FUSION_HIP_TRY(hipMemcpyAsync(d_views, views.data(), n * sizeof(DevView), hipMemcpyHostToDevice, hold.stream));
+    // per-view scratch, sized for the largest view
+    const int max_chunks = (int)((max_pixels + kScanChunk - 1) / kScanChunk);
+    uint32_t *d_hit = nullptr;
+    uint8_t *d_approved = nullptr;
+    int *d_chunk_last = nullptr, *d_carry_last = nullptr, *d_chunk_count = nullptr, *d_chunk_base = nullptr;
+    int *d_view_points = nullptr, *h_view_points = nullptr;
+    DevPoint *d_out[2] = {nullptr, nullptr}, *h_out[2] = {nullptr, nullptr};
+    FUSION_HIP_TRY(dev_alloc(max_pixels * sizeof(uint32_t), (void **)&d_hit));
+    FUSION_HIP_TRY(dev_alloc(max_pixels, (void **)&d_approved));
+    FUSION_HIP_TRY(dev_alloc((size_t)max_chunks * kMaxSrc * sizeof(int), (void **)&d_chunk_last));
+    FUSION_HIP_TRY(dev_alloc((size_t)max_chunks * kMaxSrc * sizeof(int), (void **)&d_carry_last));
+    FUSION_HIP_TRY(dev_alloc((size_t)max_chunks * sizeof(int), (void **)&d_chunk_count));
+    FUSION_HIP_TRY(dev_alloc((size_t)max_chunks * sizeof(int), (void **)&d_chunk_base));
+    FUSION_HIP_TRY(dev_alloc(2 * sizeof(int), (void **)&d_view_points));
+    FUSION_HIP_TRY(hipHostMalloc((void **)&h_view_points, 2 * sizeof(int), hipHostMallocDefault));
+    hold.pinned.push_back(h_view_points);
+    for (int b = 0; b < 2; ++b) {
+        FUSION_HIP_TRY(dev_alloc(max_pixels * sizeof(DevPoint), (void **)&d_out[b]));
+        FUSION_HIP_TRY(hipHostMalloc((void **)&h_out[b], std::max(max_pixels, size_t(1)) * sizeof(DevPoint),
+                                     hipHostMallocDefault));
+        hold.pinned.push_back(h_out[b]);
+    }
+    FUSION_HIP_TRY(hipStreamSynchronize(hold.stream));
+    const auto t_uploaded = Clock::now();
+
+    // ---- the views, in order. View i's points come back while view i + 1's kernels run, and the
+    // host forms view i's cloud entries (normal and colour are the host's) beside them.
+    std::vector<Point> cloud;
+    cloud.reserve(sc.pixels());
+    double t_wait = 0, t_copy_wait = 0, t_collect = 0;
+    auto collect = [&](size_t i) -> int {  // view i's points, in pixel order, into the cloud
+        const auto t0 = Clock::now();
+        FUSION_HIP_TRY(hipEventSynchronize(hold.copied[i & 1]));
+        t_copy_wait += secs(t0, Clock::now());
+        const DevPoint *pts = h_out[i & 1];
+        const int cnt = h_view_points[i & 1];
+        const float *nrm = sc.normals[i].data();
+        const uint8_t *img = sc.images[i].data();
+        for (int k = 0; k < cnt; ++k) {
+            const size_t q = pts[k].q;
+            Point p;
+            p.coord = F3{pts[k].x, pts[k].y, pts[k].z};
+            p.normal = F3{nrm[q * 3], nrm[q * 3 + 1], nrm[q * 3 + 2]};
+            p.color = F3{(float)img[q * 3], (float)img[q * 3 + 1], (float)img[q * 3 + 2]};
+            cloud.push_back(p);
+        }
+        t_collect += secs(t0, Clock::now());
+        return ACMMP_OK;
+    };
+    for (size_t i = 0; i < n; ++i) {
+        const int N = sc.cols[i] * sc.rows[i];
+        const int nchunks = (N + kScanChunk - 1) / kScanChunk;
+        if (N > 0) {
+            k_fusion_test<<<(N + 255) / 256, 256, 0, hold.stream>>>(d_views, (int)i, con_num_thresh, consistency_scalar,
+                                                                   d_hit, d_approved);
+            k_fusion_chunks<<<(nchunks * 32 + 255) / 256, 256, 0, hold.stream>>>(d_hit, d_approved, N, nchunks,
+                                                                                d_chunk_last, d_chunk_count);
+        }
+        k_fusion_carry<<<1, 576, 0, hold.stream>>>(nchunks, d_chunk_last, d_chunk_count, d_carry_last, d_chunk_base,
+                                                   d_view_points + (i & 1));
+        if (N > 0)
+            k_fusion_apply<<<nchunks, kScanChunk, 0, hold.stream>>>(d_views, (int)i, d_hit, d_approved, d_chunk_last,
+                                                                    d_carry_last, d_chunk_base, d_out[i & 1]);
+        FUSION_HIP_TRY(hipGetLastError());
+        FUSION_HIP_TRY(hipMemcpyAsync(h_view_points + (i & 1), d_view_points + (i & 1), sizeof(int),
+                                      hipMemcpyDeviceToHost, hold.stream));
+        if (i > 0 && (rc = collect(i - 1))) return rc;  // beside view i's kernels
+        const auto t1 = Clock::now();
+        FUSION_HIP_TRY(hipStreamSynchronize(hold.stream));
+        t_wait += secs(t1, Clock::now());
+        const int cnt = h_view_points[i & 1];
+        if (cnt < 0 || cnt > N)
+            return ffail(ACMMP_ERR_HIP, "view %d: %d points of %d pixels", problems[i].ref_image_id, cnt, N);
+        if (cnt > 0)
+            FUSION_HIP_TRY(hipMemcpyAsync(h_out[i & 1], d_out[i & 1], (size_t)cnt * sizeof(DevPoint),
+                                          hipMemcpyDeviceToHost, hold.stream));
+        FUSION_HIP_TRY(hipEventRecord(hold.copied[i & 1], hold.stream));
+    }
+    if ((rc = collect(n - 1))) return rc;
+    if (num_points) *num_points = (int)cloud.size();
+    const auto t_fused = Clock::now();
+    rc = store_ply(out + "/ACMMP_model.ply", cloud, &pool);
+    if (timing)
+        std::fprintf(stderr,
+                     "[RunFusionJacobi] load=%.3fs upload=%.3fs views=%.3fs (device_wait=%.3fs download_wait=%.3fs "
+                     "collect=%.3fs) ply=%.3fs threads=%d map_bytes=%zu points=%zu\n",
+                     secs(t_start, t_loaded), secs(t_loaded, t_uploaded), secs(t_uploaded, t_fused), t_wait,
+                     t_copy_wait, t_collect - t_copy_wait, secs(t_fused, Clock::now()), pool.size() + 1, arena_bytes,
+                     cloud.size());
+    return rc;
+}
+
+}  // extern "C"

@@ -45,6 +45,10 @@ void usage() {
         "  --no_fusion              stop after the depth/normal/cost maps\n"
         "  --multi_fusion [DIR]     with -p: prior-aware fusion against <dense>DIR (default /ACMMP)\n"
         "  --force_fusion           prior-aware fusion even without -p\n"
+        "  --fusion literal|jacobi  RunFusion's order: the reference's sequential walk on the host (default),\n"
+        "                           or on the GPU (--device; with --view_parallel rank 0's), every pixel of a\n"
+        "                           view reading the masks as they stood when the view began. The prior-aware\n"
+        "                           fusion is always literal\n"
         "  --single_match_penalty N extra consistent views required of one-sided support (0)\n"
         "  --order sequential|jacobi  pass order: the reference's (default; a geometric pass reads the maps\n"
         "                           of the views before it in the same pass) or Jacobi (= --view_parallel)\n"
@@ -70,7 +74,7 @@ int die(const char *what) {
 int main(int argc, char **argv) {
     std::string dense_folder, output_dir = "/ACMMP", mask_dir = " ", image_dir = "/images", fusion_dir = "/ACMMP";
     bool prior = false, quiet = false, triangulation = true, renamed_outdir = false, fusion = true;
-    bool multi_fusion = false, force_fusion = false;
+    bool multi_fusion = false, force_fusion = false, fusion_jacobi = false;
     float consistency_scalar = 0.3f;
     int num_consistent_thresh = 1, single_match_penalty = 0;
     int device = 0, iterations = 0, concurrent_views = 2;
@@ -109,6 +113,13 @@ int main(int argc, char **argv) {
                 return 2;
             }
             view_parallel = o == "jacobi";
+        } else if (a == "--fusion" || a.rfind("--fusion=", 0) == 0) {
+            const std::string o = a == "--fusion" ? value() : a.substr(9);
+            if (o != "literal" && o != "jacobi") {
+                std::fprintf(stderr, "acmmp_main: --fusion literal|jacobi\n");
+                return 2;
+            }
+            fusion_jacobi = o == "jacobi";
         } else if (a == "--exchange") {
             const std::string e = value();
             if (e != "rccl" && e != "tcp") {
@@ -298,8 +309,20 @@ int main(int argc, char **argv) {
         if (!quiet) std::printf("Fused %d points into %s/ACMMP_prior_model.ply\n", npts, output_folder.c_str());
         return 0;
     }
-    if (acmmp_run_fusion(dense_folder.c_str(), output_folder.c_str(), problems.data(), num_images, 1,
-                         consistency_scalar, num_consistent_thresh, image_dir.c_str(), mask_dir.c_str(), 1, &npts)) {
+    if (fusion_jacobi) {
+        // on --device; after --view_parallel on rank 0's device (LOCAL_RANK unless --device was given)
+        int fusion_device = device;
+        if (view_parallel && !device_set)
+            if (const char *lr = std::getenv("LOCAL_RANK")) fusion_device = std::atoi(lr);
+        if (acmmp_run_fusion_jacobi(dense_folder.c_str(), output_folder.c_str(), problems.data(), num_images, 1,
+                                    consistency_scalar, num_consistent_thresh, image_dir.c_str(), mask_dir.c_str(),
+                                    fusion_device, &npts)) {
+            std::fprintf(stderr, "acmmp_main: RunFusion (Jacobi order): %s\n", acmmp_fusion_last_error());
+            return 1;
+        }
+    } else if (acmmp_run_fusion(dense_folder.c_str(), output_folder.c_str(), problems.data(), num_images, 1,
+                                consistency_scalar, num_consistent_thresh, image_dir.c_str(), mask_dir.c_str(), 1,
+                                &npts)) {
         std::fprintf(stderr, "acmmp_main: RunFusion: %s\n", acmmp_fusion_last_error());
         return 1;
     }

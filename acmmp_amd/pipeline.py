@@ -216,13 +216,31 @@ def run_sequential(dense_folder: str, output_dir: str | None = None, device: int
 
 def run_fusion(dense_folder: str, output_folder: str, problems=None, geom_consistency: bool = True,
                consistency_scalar: float = 0.3, num_consistent_thresh: int = 1, image_dir: str = "/images",
-               mask_folder: str = " ", write_debug_images: bool = False) -> int:
+               mask_folder: str = " ", write_debug_images: bool = False, order: str = "literal",
+               device: int = 0) -> int:
     """RunFusion (src/acmmp_definitions.cpp:828-1043): writes
-    <output_folder>/ACMMP_model.ply; returns the number of fused points."""
+    <output_folder>/ACMMP_model.ply; returns the number of fused points.
+    order="literal" is the reference's sequential walk on the host;
+    order="jacobi" runs on HIP device `device`: every pixel of a view reads the
+    masks as they stood when the view began (acmmp_run_fusion_jacobi; no debug
+    images)."""
+    if order not in ("literal", "jacobi"):
+        raise ValueError(f"order must be 'literal' or 'jacobi', not {order!r}")
+    if order == "jacobi" and write_debug_images:
+        raise ValueError("the debug images are the literal order's: order='jacobi' writes none")
     if problems is None:
         problems = generate_sample_list(dense_folder)
     lib = _abi.load_library()
     n = C.c_int(0)
+    if order == "jacobi":
+        rc = lib.acmmp_run_fusion_jacobi(dense_folder.encode(), output_folder.encode(), _array(problems),
+                                         len(problems), int(geom_consistency), float(consistency_scalar),
+                                         int(num_consistent_thresh), image_dir.encode(), mask_folder.encode(),
+                                         int(device), C.byref(n))
+        if rc != 0:
+            raise AcmmpError(f"RunFusion (Jacobi order) failed (status {rc}): "
+                             f"{lib.acmmp_fusion_last_error().decode()}")
+        return n.value
     rc = lib.acmmp_run_fusion(dense_folder.encode(), output_folder.encode(), _array(problems), len(problems),
                               int(geom_consistency), float(consistency_scalar), int(num_consistent_thresh),
                               image_dir.encode(), mask_folder.encode(), int(write_debug_images), C.byref(n))

@@ -504,6 +504,27 @@ int acmmp_seed_planes_device(int device, const uint16_t *d_depth, int dw, int dh
 int acmmp_run_fusion(const char *dense_folder, const char *output_folder, const acmmp_problem *problems, int count,
                      int geom_consistency, float consistency_scalar, int con_num_thresh, const char *image_dir,
                      const char *mask_folder, int write_debug_images, int *num_points);
+/* ~ RunFusion (src/acmmp_definitions.cpp:828-1043) in Jacobi order, on HIP
+ * device `device`: the same inputs, tests, view and pixel order and the same
+ * <output>/ACMMP_model.ply format as acmmp_run_fusion, with two documented
+ * differences. (1) Every pixel of a view reads the masks (its
+ * own, :946, and each source's, :972, also where a view is its own source)
+ * as they stood before the view's first pixel; a view's mask writes become
+ * visible to the next view. used_list, never reset between pixels, acts as in
+ * the reference: at every approved pixel, per source slot, the target of the
+ * last pixel at or before it that passed that slot's tests is masked.
+ * (2) acos / exp are the pinned dm_acosf / dm_expf (acmmp_detmath.h), not the
+ * host's libm. A projected coordinate whose p + 0.5f is not finite or lies
+ * outside [-2^31, 2^31) is out of bounds (what the host's int() gives). No
+ * debug images. Deterministic: two runs write the same bytes. Errors as
+ * acmmp_run_fusion (acmmp_fusion_last_error); without a usable device
+ * ACMMP_ERR_HIP, nothing launched and no file written. */
+int acmmp_run_fusion_jacobi(const char *dense_folder, const char *output_folder, const acmmp_problem *problems,
+                            int count, int geom_consistency, float consistency_scalar, int con_num_thresh,
+                            const char *image_dir, const char *mask_folder, int device, int *num_points);
+/* Pixels per chunk of acmmp_run_fusion_jacobi's two-level scan (a compile-time
+ * constant of the kernels; tests size their images past it). */
+int acmmp_fusion_jacobi_scan_chunk(void);
 /* ~ RunPriorAwareFusion (src/acmmp_definitions.cpp:573-826): fuses the maps
  * of `fusion_folder` with this run's (`output_folder`) seeded maps as priors,
  * per pixel choosing the hypothesis with more consistent views

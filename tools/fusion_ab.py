@@ -5,7 +5,14 @@ RunFusion in a subprocess per configuration, configurations interleaved
 
 usage: python tools/fusion_ab.py '<json list of env dicts>' [repeat] [views] [width] [height] [nsrc]
   e.g. '[{}, {"ACMMP_HOST_THREADS": "8"}]'
-Prints one JSON line per run with RunFusion's own phase timing line.
+A configuration's "order" key is not an environment variable: "literal"
+(default) or "jacobi" (the device fusion, acmmp_run_fusion_jacobi), e.g.
+  '[{"ACMMP_LIB": "<a parent build>"}, {"order": "jacobi"}]'
+Prints one JSON line per run with the fusion's own phase timing line, the
+in-process seconds of the call alone (`s`; library load and device start-up
+are outside it) and a digest of the PLY's point set; at the end one line with
+each configuration's median and the sizes of the one-sided differences between
+the first two configurations' point sets.
 """
 import json
 import os
@@ -19,6 +26,20 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 
+def point_records(path):
+    """The PLY's 27-byte records, sorted (a point set, order-free)."""
+    import numpy as np
+    data = open(path, "rb").read()
+    body = data[data.index(b"end_header\n") + 11:]
+    rec = np.frombuffer(body, np.uint8).reshape(-1, 27)
+    return np.unique(np.ascontiguousarray(rec).view([("r", "V27")]).ravel())
+
+
+def setdiff(a, b):
+    import numpy as np
+    return np.setdiff1d(a, b)
+
+
 def main():
     import torch
     from acmmp_amd.distributed import ViewParallelPipeline
@@ -30,21 +51,38 @@ def main():
     tmp, dense = write_cfg4_dense(V, W, H, NSRC)
     ViewParallelPipeline(dense, "/ACMMP_fab", device=0).run()
     torch.cuda.synchronize()
-    code = ("import sys, time, json; sys.path.insert(0, %r); from acmmp_amd import pipeline; "
-            "t0 = time.perf_counter(); n = pipeline.run_fusion(%r, %r); "
+    # (the jacobi call is preceded by a device start-up outside the timed call: torch, already
+    # imported by the package loader, creates the context)
+    code = ("import sys, time, json; sys.path.insert(0, %r); from acmmp_amd import pipeline, _abi; "
+            "_abi.load_library(); import torch; torch.zeros(1, device='cuda'); torch.cuda.synchronize(); "
+            "kw = {'order': 'jacobi'} if sys.argv[1] == 'jacobi' else {}; "
+            "t0 = time.perf_counter(); n = pipeline.run_fusion(%r, %r, **kw); "
             "print(json.dumps({'points': n, 's': round(time.perf_counter() - t0, 3)}))"
             % (ROOT, dense, dense + "/ACMMP_fab"))
+    ply = os.path.join(dense + "/ACMMP_fab", "ACMMP_model.ply")
+    times, sets = {}, {}
     for r in range(repeat):
         for k, cfg in enumerate(configs):
+            cfg = dict(cfg)
+            order = cfg.pop("order", "literal")
             env = dict(os.environ, ACMMP_HOST_TIMING="1", **cfg)
-            p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env)
+            p = subprocess.run([sys.executable, "-c", code, order], capture_output=True, text=True, env=env)
             if p.returncode:
                 print(p.stderr[-2000:], file=sys.stderr)
                 raise SystemExit(p.returncode)
             res = json.loads(p.stdout.strip().splitlines()[-1])
-            timing = [l for l in p.stderr.splitlines() if l.startswith("[RunFusion]")]
-            print(json.dumps({"round": r, "config": k, "env": cfg, **res, "timing": timing[-1] if timing else None}),
-                  flush=True)
+            timing = [l for l in p.stderr.splitlines() if l.startswith("[RunFusion")]
+            times.setdefault(k, []).append(res["s"])
+            if k not in sets:
+                sets[k] = point_records(ply)
+            print(json.dumps({"round": r, "config": k, "order": order, "env": cfg, **res,
+                              "timing": timing[-1] if timing else None}), flush=True)
+    summary = {"median_s": {k: sorted(v)[len(v) // 2] for k, v in times.items()},
+               "points": {k: len(v) for k, v in sets.items()}}
+    if len(sets) > 1:
+        summary["only_in_config_0"] = len(setdiff(sets[0], sets[1]))
+        summary["only_in_config_1"] = len(setdiff(sets[1], sets[0]))
+    print(json.dumps(summary), flush=True)
     shutil.rmtree(tmp, ignore_errors=True)
 
 
