@@ -14,7 +14,8 @@
 //
 // What the Jacobi-order device fusion (acmmp_fusion_dev.hip) needs as well lives in
 // acmmp_fusion_host.h: world_point / project, CacheDomain, Pool, pool_for, MaskBits, Scene,
-// load_view .. resolve_sources, store_ply, the error string. This file builds without HIP.
+// FusionInputs, load_view .. resolve_sources, store_ply, the error string. This file builds
+// without HIP.
 //
 // The file, in order (RunFusion unless said otherwise):
 //   get_angle .. stage_reproject     the reference's float expressions, vectorised stages
@@ -346,11 +347,6 @@ struct CInfo {  // struct c_info
 
 struct CMetric {  // struct cmetric
     float reproj_err = 1e6, relative_depth_diff = 1e6, angle = 1e6;
-};
-
-struct FusionInputs : Scene {  // with the second map pair: this run's priors
-    std::vector<std::vector<float>> pdepths, pnormals;
-    FusionInputs(const acmmp_problem *p, size_t n) : Scene(p, n), pdepths(n), pnormals(n) {}
 };
 
 CMetric metric_of(const FusionInputs &in, size_t i, int r, int c, float ref_depth, const float *ref_normal, int src,

@@ -1,7 +1,9 @@
-// acmmp_fusion_dev.hip — RunFusion (src/acmmp_definitions.cpp:828-1043) in Jacobi order on the
-// device: acmmp_run_fusion_jacobi. The literal fusion (acmmp_fusion.cpp) walks a view's pixels one
-// after the other because an approval masks source pixels that later pixels of the SAME view then
-// skip. Here every pixel of view i reads the masks as they stood before view i's first pixel (its
+// acmmp_fusion_dev.hip — the two fusions in Jacobi order on the device: RunFusion
+// (src/acmmp_definitions.cpp:828-1043) as acmmp_run_fusion_jacobi, RunPriorAwareFusion (:573-826) as
+// acmmp_run_prior_aware_fusion_jacobi (after RunFusion's kernels below).
+// RunFusion: the literal fusion (acmmp_fusion.cpp) walks a view's pixels one after the other
+// because an approval masks source pixels that later pixels of the SAME view then skip. Here
+// every pixel of view i reads the masks as they stood before view i's first pixel (its
 // own mask bit and every source's, also when a view lists itself as a source); view i's mask writes
 // become visible to view i + 1. Nothing else changes: view order, pixel order, the float
 // expressions (world_point / project of acmmp_fusion_host.h, shared with the host), the thresholds,
@@ -25,6 +27,22 @@
 // int(p + 0.5f): the host's conversion of a NaN, an infinity or a value outside int is INT_MIN,
 // which the bounds test rejects; the device's saturates (NaN -> 0, in bounds). src_pixel tests the
 // range before converting: not finite or outside [-2^31, 2^31) is out of bounds.
+//
+// RunPriorAwareFusion has no used_list (declared at :679, never used): an approved pixel masks the
+// targets of its own chosen hypothesis's below-threshold candidates (:814-818) and nothing else, so
+// there are no stale entries and no last-hit rows. A view is
+//   k_prior_test     a thread a pixel: both hypotheses (0 = fusion_folder's maps, 1 = output_folder's,
+//                    this run's priors) against both maps of every source, the choice (:754-789);
+//                    out: the chosen hypothesis's 32-bit hit mask and a flag byte (bit 0 approved,
+//                    bit 1 the chosen hypothesis)
+//   k_fusion_chunks  the approvals' exclusive prefix, as above (the last-hit rows it also fills are
+//   k_fusion_carry   not read)
+//   k_prior_apply    its own launch after the test (fused, one pixel's write could reach another
+//                    pixel's test of the same view): an approved pixel writes its point at its
+//                    position (the chosen hypothesis in bit 31 of the pixel index) and sets the mask
+//                    bit of every hit's target, recomputed by the test's expression
+// Both calls share the host side (fuse_on_device): one upload of every view's maps, one stream,
+// view i's points copied back and collected while view i + 1's kernels run.
 #include <hip/hip_runtime.h>
 
 #include "acmmp_fusion_host.h"
@@ -44,13 +62,22 @@ struct DevView {
     int src[kMaxSrc];      // [slot j]: the source's view index
     const float *depth;    // H x W
     const float *normal;   // H x W x 3
+    const float *pdepth;   // the prior-aware fusion's second pair (this run's priors), else null
+    const float *pnormal;
     uint32_t *mask;        // bit k & 31 of word k >> 5 (MaskBits' 64-bit words, little-endian)
 };
 
-struct DevPoint {  // an approved pixel: its world point and pixel index (normal, colour: the host's)
+// an approved pixel: its world point and pixel index (normal, colour: the host's); bit 31 of q: the
+// point is the prior-aware fusion's hypothesis 1 (pixel indices fit in 27 bits)
+struct DevPoint {
     float x, y, z;
     uint32_t q;
 };
+
+// a pixel's flag byte, what a test kernel writes and the scan and apply kernels read: k_fusion_test
+// writes 0 or kFlagApproved, k_prior_test also the hypothesis it chose
+constexpr int kFlagApproved = 1;  // bit 0
+constexpr int kFlagPickShift = 1; // bit 1: the prior-aware fusion's chosen hypothesis
 
 __device__ inline bool mask_bit(const uint32_t *m, int k) { return (m[k >> 5] >> (k & 31)) & 1u; }
 
@@ -119,7 +146,7 @@ k_fusion_test(const DevView *__restrict__ views, int i, int con_num_thresh, floa
         ok = num_consistent >= con_num_thresh && (dynamic_consistency > consistency_scalar * num_consistent);
     }
     hit[q] = hits;
-    approved[q] = ok ? 1 : 0;
+    approved[q] = ok ? kFlagApproved : 0;
 }
 
 // 32 threads a chunk: thread j finds the chunk's last hit on slot j (-1: none; walks back from the
@@ -139,7 +166,7 @@ k_fusion_chunks(const uint32_t *__restrict__ hit, const uint8_t *__restrict__ ap
         }
     chunk_last[chunk * kMaxSrc + j] = last;
     int cnt = 0;
-    for (int p = b + j; p < e; p += 32) cnt += approved[p];
+    for (int p = b + j; p < e; p += 32) cnt += approved[p] & kFlagApproved;
     for (int o = 16; o > 0; o >>= 1) cnt += __shfl_down(cnt, o, 32);
     if (j == 0) chunk_count[chunk] = cnt;
 }
@@ -232,6 +259,108 @@ k_fusion_apply(const DevView *__restrict__ views, int i, const uint32_t *__restr
     }
 }
 
+// ---- RunPriorAwareFusion
+
+// metric_of + the thresholds of get_consistency_metrics (:443-516) for one of a source's two maps:
+// whether it passes, and then exp(-index) in dc (exp's value is used nowhere else)
+__device__ inline bool prior_metric(const DevView &vi, int r, int c, float ref_depth, const float *ref_normal,
+                                    const DevView &vs, int sr, int sc, float src_depth, const float *src_normal,
+                                    float &dc) {
+    if (!(src_depth > 0.0f)) return false;  // (all three metrics 1e6)
+    const F3 tmp_X = world_point(sc, sr, src_depth, vs.cam);
+    float tx, ty, proj_depth;
+    project(tmp_X, vi.cam, tx, ty, proj_depth);
+    const double dx = (double)(c - tx), dy = (double)(r - ty);
+    const float reproj_err = (float)sqrt(dx * dx + dy * dy);
+    const float relative_depth_diff = fabsf(proj_depth - ref_depth) / ref_depth;
+    if (!(reproj_err < 2.0f && relative_depth_diff < 0.01f)) return false;
+    const float angle = get_angle(ref_normal, src_normal);
+    if (!(angle < 0.174533f)) return false;
+    dc = dm_expf(-(reproj_err + 200 * relative_depth_diff + angle * 10));
+    return true;
+}
+
+__global__ void __launch_bounds__(256)
+k_prior_test(const DevView *__restrict__ views, int i, int num_consistent_thresh, int single_match_penalty,
+             float consistency_scalar, uint32_t *__restrict__ hit, uint8_t *__restrict__ flag) {
+    const DevView &vi = views[i];
+    const int N = vi.W * vi.H;
+    const int q = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (q >= N) return;
+    uint32_t hits[2] = {0, 0};
+    int pick = 0;
+    bool passing = false;
+    const float ref_depth[2] = {vi.depth[q], vi.pdepth[q]};
+    if (!mask_bit(vi.mask, q) && !(ref_depth[0] <= 0.0f && ref_depth[1] <= 0.0f)) {
+        const int r = q / vi.W, c = q - r * vi.W;
+        int nb[2] = {0, 0};
+        bool t[2] = {false, false};
+        for (int b = 0; b < 2; ++b) {
+            if (!(ref_depth[b] > 0.0f)) continue;
+            const float *ref_normal = (b ? vi.pnormal : vi.normal) + (size_t)q * 3;
+            const F3 X = world_point(c, r, ref_depth[b], vi.cam);
+            float d_cons = 0;
+            for (int j = 0; j < vi.nsrc; ++j) {  // getCandidates (:520-571)
+                const DevView &vs = views[vi.src[j]];
+                int sc, sr;
+                if (!src_pixel(X, vs, sc, sr)) continue;
+                const int sp = sr * vs.W + sc;
+                if (mask_bit(vs.mask, sp)) continue;
+                float dc0 = 0, dc1 = 0;
+                const bool t0 = prior_metric(vi, r, c, ref_depth[b], ref_normal, vs, sr, sc, vs.depth[sp],
+                                             &vs.normal[(size_t)sp * 3], dc0);
+                const bool t1 = prior_metric(vi, r, c, ref_depth[b], ref_normal, vs, sr, sc, vs.pdepth[sp],
+                                             &vs.pnormal[(size_t)sp * 3], dc1);
+                if (!t0 && !t1) continue;
+                hits[b] |= 1u << j;
+                nb[b]++;
+                d_cons += t0 && t1 ? fmaxf(dc0, dc1) : t0 ? dc0 : dc1;
+            }
+            t[b] = nb[b] >= num_consistent_thresh && d_cons > consistency_scalar * nb[b];
+        }
+        if (t[0] && t[1]) {  // (:754-789)
+            passing = true;
+            pick = nb[1] >= nb[0] ? 1 : 0;
+        } else if (t[1]) {
+            passing = nb[1] >= num_consistent_thresh + single_match_penalty;
+            pick = 1;
+        } else {
+            passing = t[0] && nb[0] >= num_consistent_thresh + single_match_penalty;
+        }
+    }
+    hit[q] = passing ? hits[pick] : 0u;
+    flag[q] = (uint8_t)((passing ? kFlagApproved : 0) | pick << kFlagPickShift);
+}
+
+__global__ void __launch_bounds__(kScanChunk)
+k_prior_apply(const DevView *__restrict__ views, int i, const uint32_t *__restrict__ hit,
+              const uint8_t *__restrict__ flag, const int *__restrict__ chunk_base, DevPoint *__restrict__ out) {
+    __shared__ int s_wave[kScanChunk / 64];
+    const DevView &vi = views[i];
+    const int N = vi.W * vi.H;
+    const int chunk = (int)blockIdx.x, tid = (int)threadIdx.x, q = chunk * kScanChunk + tid;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int f = q < N ? flag[q] : 0;
+    const bool ok = f & kFlagApproved;
+    const unsigned long long votes = __ballot(ok);
+    if (lane == 0) s_wave[wave] = __popcll(votes);
+    __syncthreads();
+    if (!ok) return;
+    int pos = chunk_base[chunk] + __popcll(votes & ((1ull << lane) - 1ull));
+    for (int w = 0; w < wave; ++w) pos += s_wave[w];
+    const int pick = f >> kFlagPickShift;
+    const int r = q / vi.W, c = q - r * vi.W;
+    const F3 X = world_point(c, r, pick ? vi.pdepth[q] : vi.depth[q], vi.cam);
+    out[pos] = DevPoint{X.x, X.y, X.z, (uint32_t)q | (uint32_t)pick << 31};
+    for (uint32_t h = hit[q]; h; h &= h - 1) {
+        const DevView &vs = views[vi.src[__ffs((int)h) - 1]];
+        int sc, sr;
+        if (!src_pixel(X, vs, sc, sr)) continue;  // (a hit passed this very test in k_prior_test)
+        const int sp = sr * vs.W + sc;
+        atomicOr(&vs.mask[sp >> 5], 1u << (sp & 31));
+    }
+}
+
 using Clock = std::chrono::steady_clock;
 double secs(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double>(b - a).count(); }
 
@@ -259,43 +388,33 @@ struct DevHold {
 
 size_t align256(size_t n) { return (n + 255) / 256 * 256; }
 
-}  // namespace
-
-extern "C" {
-
-int acmmp_fusion_jacobi_scan_chunk(void) { return kScanChunk; }
-
-int acmmp_run_fusion_jacobi(const char *dense_folder, const char *output_folder, const acmmp_problem *problems,
-                            int count, int geom_consistency, float consistency_scalar, int con_num_thresh,
-                            const char *image_dir, const char *mask_folder, int device, int *num_points) {
-    if (!dense_folder || !output_folder || !problems || count <= 0) return ffail(ACMMP_ERR_ARG, "bad args");
+// checked before any load: without a usable device nothing is launched and no file written
+int need_device(const char *what, int device) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess) ndev = 0;
     if (device < 0 || device >= ndev)
-        return ffail(ACMMP_ERR_HIP, "RunFusion in Jacobi order needs a HIP device: device %d of %d asked for", device,
+        return ffail(ACMMP_ERR_HIP, "%s in Jacobi order needs a HIP device: device %d of %d asked for", what, device,
                      ndev);
-    const std::string dense = dense_folder, out = output_folder;
-    const std::string image_folder = dense + (image_dir ? image_dir : "/images");
-    const bool use_masks = mask_folder && std::string(mask_folder) != " " && mask_folder[0] != 0;
-    const char *suffix = geom_consistency ? "/depths_geom.dmb" : "/depths.dmb";
-    const size_t n = (size_t)count;
+    return ACMMP_OK;
+}
+
+// what the two calls differ in once their views are loaded
+struct JacobiCall {
+    const std::vector<std::vector<float>> *pdepths, *pnormals;  // the prior-aware fusion's second pair, else null
+    float consistency_scalar;
+    int num_consistent_thresh, single_match_penalty;
+    const char *tag;  // of the ACMMP_HOST_TIMING line
+    std::string ply;
+};
+
+// The loaded views (masks assigned, sources resolved) through the device, view by view, into call.ply.
+int fuse_on_device(Scene &sc, const JacobiCall &call, int device, Pool &pool, Clock::time_point t_start,
+                   int *num_points) {
+    const acmmp_problem *problems = sc.problems;
+    const size_t n = sc.rows.size();
+    const bool prior = call.pdepths != nullptr;
     const bool timing = std::getenv("ACMMP_HOST_TIMING") != nullptr;
-    const auto t_start = Clock::now();
-    Scene sc(problems, n);
-    Pool pool;
-    // the literal fusion's loads, on the pool (acmmp_run_fusion)
-    int rc = pool_for(pool, (int)n, [&](int vi) -> int {
-        const size_t i = (size_t)vi;
-        const int id = problems[i].ref_image_id;
-        const int load_rc = load_view(sc, i, image_folder, dense, result_folder(out, id), suffix);
-        if (load_rc) return load_rc;
-        sc.masks[i].assign((size_t)sc.cols[i] * sc.rows[i]);
-        if (!use_masks) return (int)ACMMP_OK;
-        return load_initial_mask(dense + "/" + mask_folder + "/" + id8(id) + ".png", sc.cols[i], sc.rows[i],
-                                 sc.masks[i]);
-    });
-    if (!rc) rc = resolve_sources(sc);
-    if (rc) return rc;
+    int rc = ACMMP_OK;
     size_t max_pixels = 0;
     for (size_t i = 0; i < n; ++i) {
         if ((size_t)sc.cols[i] * sc.rows[i] > (size_t(1) << 27) || problems[i].num_src_images > kMaxSrc)
@@ -318,7 +437,7 @@ int acmmp_run_fusion_jacobi(const char *dense_folder, const char *output_folder,
     size_t arena_bytes = 0;
     for (size_t i = 0; i < n; ++i) {
         const size_t N = (size_t)sc.cols[i] * sc.rows[i];
-        arena_bytes += align256(N * sizeof(float)) + align256(N * 3 * sizeof(float)) +
+        arena_bytes += (prior ? 2 : 1) * (align256(N * sizeof(float)) + align256(N * 3 * sizeof(float))) +
                        align256(sc.masks[i].w.size() * sizeof(uint64_t));
     }
     char *arena = nullptr;
@@ -341,7 +460,9 @@ int acmmp_run_fusion_jacobi(const char *dense_folder, const char *output_folder,
         v.depth = (const float *)put(sc.depths[i].data(), N * sizeof(float));
         v.normal = (const float *)put(sc.normals[i].data(), N * 3 * sizeof(float));
         v.mask = (uint32_t *)put(sc.masks[i].w.data(), sc.masks[i].w.size() * sizeof(uint64_t));
-        if (!v.depth || !v.normal || !v.mask)
+        v.pdepth = prior ? (const float *)put((*call.pdepths)[i].data(), N * sizeof(float)) : nullptr;
+        v.pnormal = prior ? (const float *)put((*call.pnormals)[i].data(), N * 3 * sizeof(float)) : nullptr;
+        if (!v.depth || !v.normal || !v.mask || (prior && (!v.pdepth || !v.pnormal)))
             return ffail(ACMMP_ERR_HIP, "upload of view %d failed: %s", problems[i].ref_image_id,
                          hipGetErrorString(hipGetLastError()));
     }
@@ -384,10 +505,11 @@ int acmmp_run_fusion_jacobi(const char *dense_folder, const char *output_folder,
         t_copy_wait += secs(t0, Clock::now());
         const DevPoint *pts = h_out[i & 1];
         const int cnt = h_view_points[i & 1];
-        const float *nrm = sc.normals[i].data();
+        const float *normal[2] = {sc.normals[i].data(), prior ? (*call.pnormals)[i].data() : nullptr};
         const uint8_t *img = sc.images[i].data();
         for (int k = 0; k < cnt; ++k) {
-            const size_t q = pts[k].q;
+            const size_t q = pts[k].q & 0x7fffffffu;
+            const float *nrm = normal[pts[k].q >> 31];  // the chosen hypothesis's map
             Point p;
             p.coord = F3{pts[k].x, pts[k].y, pts[k].z};
             p.normal = F3{nrm[q * 3], nrm[q * 3 + 1], nrm[q * 3 + 2]};
@@ -401,14 +523,22 @@ int acmmp_run_fusion_jacobi(const char *dense_folder, const char *output_folder,
         const int N = sc.cols[i] * sc.rows[i];
         const int nchunks = (N + kScanChunk - 1) / kScanChunk;
         if (N > 0) {
-            k_fusion_test<<<(N + 255) / 256, 256, 0, hold.stream>>>(d_views, (int)i, con_num_thresh, consistency_scalar,
-                                                                   d_hit, d_approved);
+            if (prior)
+                k_prior_test<<<(N + 255) / 256, 256, 0, hold.stream>>>(d_views, (int)i, call.num_consistent_thresh,
+                                                                      call.single_match_penalty,
+                                                                      call.consistency_scalar, d_hit, d_approved);
+            else
+                k_fusion_test<<<(N + 255) / 256, 256, 0, hold.stream>>>(d_views, (int)i, call.num_consistent_thresh,
+                                                                       call.consistency_scalar, d_hit, d_approved);
             k_fusion_chunks<<<(nchunks * 32 + 255) / 256, 256, 0, hold.stream>>>(d_hit, d_approved, N, nchunks,
                                                                                 d_chunk_last, d_chunk_count);
         }
         k_fusion_carry<<<1, 576, 0, hold.stream>>>(nchunks, d_chunk_last, d_chunk_count, d_carry_last, d_chunk_base,
                                                    d_view_points + (i & 1));
-        if (N > 0)
+        if (N > 0 && prior)
+            k_prior_apply<<<nchunks, kScanChunk, 0, hold.stream>>>(d_views, (int)i, d_hit, d_approved, d_chunk_base,
+                                                                   d_out[i & 1]);
+        else if (N > 0)
             k_fusion_apply<<<nchunks, kScanChunk, 0, hold.stream>>>(d_views, (int)i, d_hit, d_approved, d_chunk_last,
                                                                     d_carry_last, d_chunk_base, d_out[i & 1]);
         FUSION_HIP_TRY(hipGetLastError());
@@ -429,15 +559,84 @@ int acmmp_run_fusion_jacobi(const char *dense_folder, const char *output_folder,
     if ((rc = collect(n - 1))) return rc;
     if (num_points) *num_points = (int)cloud.size();
     const auto t_fused = Clock::now();
-    rc = store_ply(out + "/ACMMP_model.ply", cloud, &pool);
+    rc = store_ply(call.ply, cloud, &pool);
     if (timing)
         std::fprintf(stderr,
-                     "[RunFusionJacobi] load=%.3fs upload=%.3fs views=%.3fs (device_wait=%.3fs download_wait=%.3fs "
+                     "[%s] load=%.3fs upload=%.3fs views=%.3fs (device_wait=%.3fs download_wait=%.3fs "
                      "collect=%.3fs) ply=%.3fs threads=%d map_bytes=%zu points=%zu\n",
-                     secs(t_start, t_loaded), secs(t_loaded, t_uploaded), secs(t_uploaded, t_fused), t_wait,
+                     call.tag, secs(t_start, t_loaded), secs(t_loaded, t_uploaded), secs(t_uploaded, t_fused), t_wait,
                      t_copy_wait, t_collect - t_copy_wait, secs(t_fused, Clock::now()), pool.size() + 1, arena_bytes,
                      cloud.size());
     return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int acmmp_fusion_jacobi_scan_chunk(void) { return kScanChunk; }
+
+int acmmp_run_fusion_jacobi(const char *dense_folder, const char *output_folder, const acmmp_problem *problems,
+                            int count, int geom_consistency, float consistency_scalar, int con_num_thresh,
+                            const char *image_dir, const char *mask_folder, int device, int *num_points) {
+    if (!dense_folder || !output_folder || !problems || count <= 0) return ffail(ACMMP_ERR_ARG, "bad args");
+    if (need_device("RunFusion", device)) return ACMMP_ERR_HIP;
+    const std::string dense = dense_folder, out = output_folder;
+    const std::string image_folder = dense + (image_dir ? image_dir : "/images");
+    const bool use_masks = mask_folder && std::string(mask_folder) != " " && mask_folder[0] != 0;
+    const char *suffix = geom_consistency ? "/depths_geom.dmb" : "/depths.dmb";
+    const size_t n = (size_t)count;
+    const auto t_start = Clock::now();
+    Scene sc(problems, n);
+    Pool pool;
+    // the literal fusion's loads, on the pool (acmmp_run_fusion)
+    int rc = pool_for(pool, (int)n, [&](int vi) -> int {
+        const size_t i = (size_t)vi;
+        const int id = problems[i].ref_image_id;
+        const int load_rc = load_view(sc, i, image_folder, dense, result_folder(out, id), suffix);
+        if (load_rc) return load_rc;
+        sc.masks[i].assign((size_t)sc.cols[i] * sc.rows[i]);
+        if (!use_masks) return (int)ACMMP_OK;
+        return load_initial_mask(dense + "/" + mask_folder + "/" + id8(id) + ".png", sc.cols[i], sc.rows[i],
+                                 sc.masks[i]);
+    });
+    if (!rc) rc = resolve_sources(sc);
+    if (rc) return rc;
+    const JacobiCall call{nullptr, nullptr, consistency_scalar, con_num_thresh, 0, "RunFusionJacobi",
+                          out + "/ACMMP_model.ply"};
+    return fuse_on_device(sc, call, device, pool, t_start, num_points);
+}
+
+int acmmp_run_prior_aware_fusion_jacobi(const char *dense_folder, const char *output_folder,
+                                        const char *fusion_folder, const acmmp_problem *problems, int count,
+                                        int geom_consistency, float consistency_scalar, int num_consistent_thresh,
+                                        int single_match_penalty, int device, int *num_points) {
+    if (!dense_folder || !output_folder || !fusion_folder || !problems || count <= 0)
+        return ffail(ACMMP_ERR_ARG, "bad args");
+    if (need_device("RunPriorAwareFusion", device)) return ACMMP_ERR_HIP;
+    const std::string dense = dense_folder, out = output_folder, fus = fusion_folder;
+    const char *suffix = geom_consistency ? "/depths_geom.dmb" : "/depths.dmb";
+    const size_t n = (size_t)count;
+    const auto t_start = Clock::now();
+    FusionInputs in(problems, n);
+    Pool pool;
+    // the literal call's loads (acmmp_run_prior_aware_fusion), on the pool; masks start all zero
+    int rc = pool_for(pool, (int)n, [&](int vi) -> int {
+        const size_t i = (size_t)vi;
+        const int id = problems[i].ref_image_id;
+        int load_rc = load_view(in, i, dense + "/images", dense, result_folder(fus, id), suffix);
+        int h = 0, w = 0;
+        if (!load_rc) load_rc = read_maps(result_folder(out, id), suffix, id, in.pdepths[i], in.pnormals[i], h, w);
+        if (load_rc) return load_rc;
+        if (h != in.rows[i] || w != in.cols[i]) return ffail(ACMMP_ERR_IO, "map sizes of view %d disagree", id);
+        in.masks[i].assign((size_t)w * h);
+        return (int)ACMMP_OK;
+    });
+    if (!rc) rc = resolve_sources(in);
+    if (rc) return rc;
+    const JacobiCall call{&in.pdepths, &in.pnormals, consistency_scalar, num_consistent_thresh, single_match_penalty,
+                          "RunPriorAwareFusionJacobi", out + "/ACMMP_prior_model.ply"};
+    return fuse_on_device(in, call, device, pool, t_start, num_points);
 }
 
 }  // extern "C"

@@ -1,11 +1,11 @@
 // acmmp_fusion_host.h — what the fusions' host code shares (internal, all inline):
 // acmmp_fusion.cpp (RunFusion literal, RunPriorAwareFusion) and acmmp_fusion_dev.hip
-// (RunFusion in Jacobi order on the device). No HIP in here: acmmp_fusion.cpp builds
+// (both fusions in Jacobi order on the device). No HIP in here: acmmp_fusion.cpp builds
 // with a plain C++ compiler.
 //   f_err, ffail                     the message behind acmmp_fusion_last_error (one per thread)
 //   world_point, project             the reference's float expressions (host and device)
 //   CacheDomain, Pool, pool_for      one L3 domain: the caller walks, workers do the rest
-//   MaskBits, Scene                  a fusion's inputs; masks one bit a pixel
+//   MaskBits, Scene, FusionInputs    a fusion's inputs; masks one bit a pixel
 //   load_view .. resolve_sources     one view loader and source lookup for all fusions
 //   store_ply                        27-byte records in chunks (pool or caller)
 #ifndef ACMMP_FUSION_HOST_H_
@@ -325,6 +325,11 @@ struct Scene {
         for (size_t i = 0; i < rows.size(); ++i) total += (size_t)cols[i] * rows[i];
         return total;
     }
+};
+
+struct FusionInputs : Scene {  // the prior-aware fusions': with the second map pair, this run's priors
+    std::vector<std::vector<float>> pdepths, pnormals;
+    FusionInputs(const acmmp_problem *p, size_t n) : Scene(p, n), pdepths(n), pnormals(n) {}
 };
 
 // depths[_geom].dmb and normals.dmb of view `id` in `folder`: one size, 1 and 3 bands

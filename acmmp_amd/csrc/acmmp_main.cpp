@@ -8,7 +8,8 @@
 // library's ports (acmmp_fusion.cpp): RunFusion into <out>/ACMMP_model.ply, or
 // with -p --multi_fusion [DIR] / --force_fusion RunPriorAwareFusion against
 // the reconstruction in <dense>DIR (default /ACMMP) into
-// <out>/ACMMP_prior_model.ply.
+// <out>/ACMMP_prior_model.ply. --fusion jacobi runs whichever of the two it is
+// on the GPU (acmmp_fusion_dev.hip).
 #include <sys/stat.h>
 
 #include <cstdio>
@@ -45,10 +46,10 @@ void usage() {
         "  --no_fusion              stop after the depth/normal/cost maps\n"
         "  --multi_fusion [DIR]     with -p: prior-aware fusion against <dense>DIR (default /ACMMP)\n"
         "  --force_fusion           prior-aware fusion even without -p\n"
-        "  --fusion literal|jacobi  RunFusion's order: the reference's sequential walk on the host (default),\n"
-        "                           or on the GPU (--device; with --view_parallel rank 0's), every pixel of a\n"
-        "                           view reading the masks as they stood when the view began. The prior-aware\n"
-        "                           fusion is always literal\n"
+        "  --fusion literal|jacobi  the fusion's order, RunFusion's or the prior-aware one's: the reference's\n"
+        "                           sequential walk on the host (default), or on the GPU (--device; with\n"
+        "                           --view_parallel rank 0's), every pixel of a view reading the masks as they\n"
+        "                           stood when the view began\n"
         "  --single_match_penalty N extra consistent views required of one-sided support (0)\n"
         "  --order sequential|jacobi  pass order: the reference's (default; a geometric pass reads the maps\n"
         "                           of the views before it in the same pass) or Jacobi (= --view_parallel)\n"
@@ -298,11 +299,24 @@ int main(int argc, char **argv) {
     }
     if (!fusion) return 0;
     int npts = 0;
+    // --fusion jacobi: on --device; after --view_parallel on rank 0's device (LOCAL_RANK unless --device was given)
+    int fusion_device = device;
+    if (view_parallel && !device_set)
+        if (const char *lr = std::getenv("LOCAL_RANK")) fusion_device = std::atoi(lr);
     if ((prior && multi_fusion) || force_fusion) {
         const std::string fusion_folder = dense_folder + fusion_dir;
-        if (acmmp_run_prior_aware_fusion(dense_folder.c_str(), output_folder.c_str(), fusion_folder.c_str(),
-                                         problems.data(), num_images, 1, consistency_scalar, num_consistent_thresh,
-                                         single_match_penalty, &npts)) {
+        if (fusion_jacobi) {
+            if (acmmp_run_prior_aware_fusion_jacobi(dense_folder.c_str(), output_folder.c_str(), fusion_folder.c_str(),
+                                                    problems.data(), num_images, 1, consistency_scalar,
+                                                    num_consistent_thresh, single_match_penalty, fusion_device,
+                                                    &npts)) {
+                std::fprintf(stderr, "acmmp_main: RunPriorAwareFusion (Jacobi order): %s\n",
+                             acmmp_fusion_last_error());
+                return 1;
+            }
+        } else if (acmmp_run_prior_aware_fusion(dense_folder.c_str(), output_folder.c_str(), fusion_folder.c_str(),
+                                                problems.data(), num_images, 1, consistency_scalar,
+                                                num_consistent_thresh, single_match_penalty, &npts)) {
             std::fprintf(stderr, "acmmp_main: RunPriorAwareFusion: %s\n", acmmp_fusion_last_error());
             return 1;
         }
@@ -310,10 +324,6 @@ int main(int argc, char **argv) {
         return 0;
     }
     if (fusion_jacobi) {
-        // on --device; after --view_parallel on rank 0's device (LOCAL_RANK unless --device was given)
-        int fusion_device = device;
-        if (view_parallel && !device_set)
-            if (const char *lr = std::getenv("LOCAL_RANK")) fusion_device = std::atoi(lr);
         if (acmmp_run_fusion_jacobi(dense_folder.c_str(), output_folder.c_str(), problems.data(), num_images, 1,
                                     consistency_scalar, num_consistent_thresh, image_dir.c_str(), mask_dir.c_str(),
                                     fusion_device, &npts)) {

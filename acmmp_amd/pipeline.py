@@ -251,13 +251,29 @@ def run_fusion(dense_folder: str, output_folder: str, problems=None, geom_consis
 
 def run_prior_aware_fusion(dense_folder: str, output_folder: str, fusion_folder: str, problems=None,
                            geom_consistency: bool = True, consistency_scalar: float = 0.3,
-                           num_consistent_thresh: int = 1, single_match_penalty: int = 0) -> int:
+                           num_consistent_thresh: int = 1, single_match_penalty: int = 0, order: str = "literal",
+                           device: int = 0) -> int:
     """RunPriorAwareFusion (src/acmmp_definitions.cpp:573-826): writes
-    <output_folder>/ACMMP_prior_model.ply; returns the number of points."""
+    <output_folder>/ACMMP_prior_model.ply; returns the number of points.
+    order="literal" is the reference's sequential walk on the host;
+    order="jacobi" runs on HIP device `device`, every pixel of a view reading
+    the masks as they stood when the view began
+    (acmmp_run_prior_aware_fusion_jacobi)."""
+    if order not in ("literal", "jacobi"):
+        raise ValueError(f"order must be 'literal' or 'jacobi', not {order!r}")
     if problems is None:
         problems = generate_sample_list(dense_folder)
     lib = _abi.load_library()
     n = C.c_int(0)
+    if order == "jacobi":
+        rc = lib.acmmp_run_prior_aware_fusion_jacobi(
+            dense_folder.encode(), output_folder.encode(), fusion_folder.encode(), _array(problems), len(problems),
+            int(geom_consistency), float(consistency_scalar), int(num_consistent_thresh), int(single_match_penalty),
+            int(device), C.byref(n))
+        if rc != 0:
+            raise AcmmpError(f"RunPriorAwareFusion (Jacobi order) failed (status {rc}): "
+                             f"{lib.acmmp_fusion_last_error().decode()}")
+        return n.value
     rc = lib.acmmp_run_prior_aware_fusion(dense_folder.encode(), output_folder.encode(), fusion_folder.encode(),
                                           _array(problems), len(problems), int(geom_consistency),
                                           float(consistency_scalar), int(num_consistent_thresh),

@@ -538,7 +538,28 @@ int acmmp_run_prior_aware_fusion(const char *dense_folder, const char *output_fo
                                  const acmmp_problem *problems, int count, int geom_consistency,
                                  float consistency_scalar, int num_consistent_thresh, int single_match_penalty,
                                  int *num_points);
-/* Message of the last failing acmmp_run_fusion / _prior_aware_fusion on this thread. */
+/* ~ RunPriorAwareFusion (src/acmmp_definitions.cpp:573-826) in Jacobi order,
+ * on HIP device `device`: the same inputs, per-pixel tests and choice, view
+ * and pixel order and the same <output>/ACMMP_prior_model.ply as
+ * acmmp_run_prior_aware_fusion, with two documented differences (DESIGN.md
+ * §8). (1) Every pixel of a view reads the masks (its own, :684, and each
+ * source's, :550, also where a view is its own source) as they stood before
+ * the view's first pixel; a view's mask writes become visible to the next
+ * view. An approved pixel masks the targets of its chosen hypothesis's
+ * below-threshold candidates (:814-818), nothing else (used_list, :679, is
+ * never used). (2) acos / exp are the pinned dm_acosf / dm_expf
+ * (acmmp_detmath.h), not the host's libm. A projected coordinate whose
+ * p + 0.5f is not finite or lies outside [-2^31, 2^31) is out of bounds (what
+ * the host's int() gives). No mask argument, as the literal call.
+ * Deterministic: two runs write the same bytes. Errors as
+ * acmmp_run_prior_aware_fusion (acmmp_fusion_last_error), the views' limits
+ * (32 sources, 2^27 pixels: ACMMP_ERR_ARG) as acmmp_run_fusion_jacobi; without
+ * a usable device ACMMP_ERR_HIP, nothing launched and no file written. */
+int acmmp_run_prior_aware_fusion_jacobi(const char *dense_folder, const char *output_folder,
+                                        const char *fusion_folder, const acmmp_problem *problems, int count,
+                                        int geom_consistency, float consistency_scalar, int num_consistent_thresh,
+                                        int single_match_penalty, int device, int *num_points);
+/* Message of the last failing acmmp_run_fusion / _prior_aware_fusion (either order) on this thread. */
 const char *acmmp_fusion_last_error(void);
 
 /* Message of the last failing driver call on this thread ("" when none). */

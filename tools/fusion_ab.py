@@ -8,6 +8,11 @@ usage: python tools/fusion_ab.py '<json list of env dicts>' [repeat] [views] [wi
 A configuration's "order" key is not an environment variable: "literal"
 (default) or "jacobi" (the device fusion, acmmp_run_fusion_jacobi), e.g.
   '[{"ACMMP_LIB": "<a parent build>"}, {"order": "jacobi"}]'
+A configuration's "fusion" key, not an environment variable either, picks the
+call: "run" (default, RunFusion) or "prior" (RunPriorAwareFusion, in either
+order). With a "prior" configuration the driver runs a second time with another
+seed into a second output folder: that reconstruction is the call's output
+folder (its maps are the priors), the first one its fusion folder.
 Prints one JSON line per run with the fusion's own phase timing line, the
 in-process seconds of the call alone (`s`; library load and device start-up
 are outside it) and a digest of the PLY's point set; at the end one line with
@@ -50,32 +55,37 @@ def main():
     V, W, H, NSRC = (int(a[k]) if len(a) > k else d for k, d in zip(range(3, 7), (49, 1600, 1200, 20)))
     tmp, dense = write_cfg4_dense(V, W, H, NSRC)
     ViewParallelPipeline(dense, "/ACMMP_fab", device=0).run()
+    if any(cfg.get("fusion") == "prior" for cfg in configs):
+        ViewParallelPipeline(dense, "/ACMMP_fab2", device=0, seed=4321).run()
     torch.cuda.synchronize()
     # (the jacobi call is preceded by a device start-up outside the timed call: torch, already
     # imported by the package loader, creates the context)
     code = ("import sys, time, json; sys.path.insert(0, %r); from acmmp_amd import pipeline, _abi; "
             "_abi.load_library(); import torch; torch.zeros(1, device='cuda'); torch.cuda.synchronize(); "
-            "kw = {'order': 'jacobi'} if sys.argv[1] == 'jacobi' else {}; "
-            "t0 = time.perf_counter(); n = pipeline.run_fusion(%r, %r, **kw); "
+            "kw = {'order': 'jacobi'} if sys.argv[1] == 'jacobi' else {}; d, out, out2 = %r, %r, %r; "
+            "t0 = time.perf_counter(); "
+            "n = pipeline.run_prior_aware_fusion(d, out2, out, **kw) if sys.argv[2] == 'prior' else "
+            "pipeline.run_fusion(d, out, **kw); "
             "print(json.dumps({'points': n, 's': round(time.perf_counter() - t0, 3)}))"
-            % (ROOT, dense, dense + "/ACMMP_fab"))
-    ply = os.path.join(dense + "/ACMMP_fab", "ACMMP_model.ply")
+            % (ROOT, dense, dense + "/ACMMP_fab", dense + "/ACMMP_fab2"))
+    plys = {"run": os.path.join(dense + "/ACMMP_fab", "ACMMP_model.ply"),
+            "prior": os.path.join(dense + "/ACMMP_fab2", "ACMMP_prior_model.ply")}
     times, sets = {}, {}
     for r in range(repeat):
         for k, cfg in enumerate(configs):
             cfg = dict(cfg)
-            order = cfg.pop("order", "literal")
+            order, fusion = cfg.pop("order", "literal"), cfg.pop("fusion", "run")
             env = dict(os.environ, ACMMP_HOST_TIMING="1", **cfg)
-            p = subprocess.run([sys.executable, "-c", code, order], capture_output=True, text=True, env=env)
+            p = subprocess.run([sys.executable, "-c", code, order, fusion], capture_output=True, text=True, env=env)
             if p.returncode:
                 print(p.stderr[-2000:], file=sys.stderr)
                 raise SystemExit(p.returncode)
             res = json.loads(p.stdout.strip().splitlines()[-1])
-            timing = [l for l in p.stderr.splitlines() if l.startswith("[RunFusion")]
+            timing = [l for l in p.stderr.splitlines() if l.startswith(("[RunFusion", "[RunPriorAwareFusion"))]
             times.setdefault(k, []).append(res["s"])
             if k not in sets:
-                sets[k] = point_records(ply)
-            print(json.dumps({"round": r, "config": k, "order": order, "env": cfg, **res,
+                sets[k] = point_records(plys[fusion])
+            print(json.dumps({"round": r, "config": k, "fusion": fusion, "order": order, "env": cfg, **res,
                               "timing": timing[-1] if timing else None}), flush=True)
     summary = {"median_s": {k: sorted(v)[len(v) // 2] for k, v in times.items()},
                "points": {k: len(v) for k, v in sets.items()}}
