@@ -139,6 +139,31 @@ class PassOptions(C.Structure):
     ]
 
 
+class FusionView(C.Structure):
+    """acmmp_fusion_view: one view of acmmp_fuse_views_jacobi, maps in device memory."""
+    _fields_ = [
+        ("cam", Camera),
+        ("num_src", C.c_int32),
+        ("src", C.c_int32 * 32),
+        ("d_depth", C.c_void_p),
+        ("depth_stride", C.c_int64),
+        ("d_normal", C.c_void_p),
+        ("normal_stride", C.c_int64),
+        ("d_bgr", C.c_void_p),
+        ("d_mask", C.c_void_p),
+    ]
+
+
+class CloudBuffers(C.Structure):
+    """acmmp_cloud_buffers: the device arrays acmmp_fuse_views_jacobi writes the cloud into."""
+    _fields_ = [
+        ("d_xyz", C.c_void_p),
+        ("d_normal", C.c_void_p),
+        ("d_rgb", C.c_void_p),
+        ("capacity", C.c_int64),
+    ]
+
+
 _FP = C.POINTER(C.c_float)
 _U32P = C.POINTER(C.c_uint32)
 class BandHalo(C.Structure):
@@ -236,6 +261,11 @@ SIGNATURES = {
     "acmmp_run_fusion_jacobi": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(Problem), C.c_int, C.c_int, C.c_float,
                                           C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_int)]),
     "acmmp_fusion_jacobi_scan_chunk": (C.c_int, []),
+    "acmmp_fuse_views_jacobi": (C.c_int, [C.c_int, C.POINTER(FusionView), C.c_int, C.c_float, C.c_int,
+                                          C.POINTER(CloudBuffers), C.c_void_p, C.POINTER(C.c_int64)]),
+    "acmmp_write_ply_points": (C.c_int, [C.c_char_p, _FP, _FP, C.POINTER(C.c_uint8), C.c_int64]),
+    "acmmp_resize_bilinear_u8": (C.c_int, [C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8),
+                                           C.c_int, C.c_int]),
     "acmmp_fusion_last_error": (C.c_char_p, []),
     "acmmp_run_prior_aware_fusion": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(Problem), C.c_int,
                                                C.c_int, C.c_float, C.c_int, C.c_int, C.POINTER(C.c_int)]),

@@ -418,6 +418,23 @@ extern "C" {
 
 const char *acmmp_fusion_last_error(void) { return f_err.c_str(); }
 
+// the host ends of the in-memory fusion (acmmp_fuse_views_jacobi, acmmp_fusion_dev.hip): in this
+// unit, which needs no HIP, so the sanitizer tier builds them with a plain C++ compiler
+int acmmp_write_ply_points(const char *path, const float *xyz, const float *normal, const uint8_t *rgb, int64_t n) {
+    if (!path || n < 0 || (n > 0 && (!xyz || !normal || !rgb)))
+        return ffail(ACMMP_ERR_ARG, "acmmp_write_ply_points: null path or array, or n below 0");
+    if (n > INT32_MAX) return ffail(ACMMP_ERR_ARG, "acmmp_write_ply_points: %lld points exceed the header's int", (long long)n);
+    Pool pool;
+    return store_ply_arrays(path, xyz, normal, rgb, (size_t)n, &pool);
+}
+
+int acmmp_resize_bilinear_u8(const uint8_t *src, int sw, int sh, int channels, uint8_t *dst, int dw, int dh) {
+    if (!src || !dst || sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0 || channels < 1 || channels > 4)
+        return ffail(ACMMP_ERR_ARG, "acmmp_resize_bilinear_u8: null image, empty size or channels outside 1..4");
+    resize_u8(src, sw, sh, channels, dst, dw, dh);
+    return ACMMP_OK;
+}
+
 int acmmp_run_fusion(const char *dense_folder, const char *output_folder, const acmmp_problem *problems, int count,
                      int geom_consistency, float consistency_scalar, int con_num_thresh, const char *image_dir,
                      const char *mask_folder, int write_debug_images, int *num_points) {

@@ -43,6 +43,13 @@
 //                    bit of every hit's target, recomputed by the test's expression
 // Both calls share the host side (fuse_on_device): one upload of every view's maps, one stream,
 // view i's points copied back and collected while view i + 1's kernels run.
+//
+// acmmp_fuse_views_jacobi is RunFusion's rule over views that already lie in device memory
+// (fuse_views_on_device): depth and normal read through strides (a float4 planes tensor serves as
+// both), byte masks packed by k_mask_pack, the same test / chunks / carry kernels, and
+// k_fusion_apply<true>, which writes whole points (xyz, normal, r g b) into the caller's arrays at
+// the running total k_fusion_carry keeps on the device + the position in the view, guarded by the
+// arrays' capacity. All on the caller's stream, no wait between views, one at the end for the count.
 #include <hip/hip_runtime.h>
 
 #include "acmmp_fusion_host.h"
@@ -60,11 +67,26 @@ struct DevView {
     acmmp_camera cam;      // at the maps' size
     int W, H, nsrc;
     int src[kMaxSrc];      // [slot j]: the source's view index
-    const float *depth;    // H x W
-    const float *normal;   // H x W x 3
+    const float *depth;    // pixel q's depth at depth[q * dstride]
+    const float *normal;   // ... its normal at normal[q * nstride + 0..2]
+    long long dstride, nstride;  // the folder calls' maps: 1 and 3; float4 planes: 4 and 4
     const float *pdepth;   // the prior-aware fusion's second pair (this run's priors), else null
-    const float *pnormal;
+    const float *pnormal;  // (H x W and H x W x 3, no strides)
+    const uint8_t *bgr;    // H x W x 3, the in-memory fusion's colours (null: 0, 0, 0); else unused
     uint32_t *mask;        // bit k & 31 of word k >> 5 (MaskBits' 64-bit words, little-endian)
+};
+
+__device__ inline float depth_at(const DevView &v, int q) { return v.depth[(long long)q * v.dstride]; }
+__device__ inline const float *normal_at(const DevView &v, int q) { return v.normal + (long long)q * v.nstride; }
+
+// where the in-memory fusion's apply step writes whole points (acmmp_cloud_buffers), and the running
+// total k_fusion_carry keeps: total[0] = the points of the views before this one (this view's
+// output base), total[1] = with this view's
+struct DevCloud {
+    float *xyz, *normal;
+    uint8_t *rgb;
+    long long capacity;
+    const long long *total;
 };
 
 // an approved pixel: its world point and pixel index (normal, colour: the host's); bit 31 of q: the
@@ -113,7 +135,7 @@ k_fusion_test(const DevView *__restrict__ views, int i, int con_num_thresh, floa
     if (q >= N) return;
     uint32_t hits = 0;
     bool ok = false;
-    const float ref_depth = vi.depth[q];
+    const float ref_depth = depth_at(vi, q);
     if (!mask_bit(vi.mask, q) && !(ref_depth <= 0.0f || ref_depth >= vi.cam.depth_max)) {
         const int r = q / vi.W, c = q - r * vi.W;
         const F3 X = world_point(c, r, ref_depth, vi.cam);
@@ -125,7 +147,7 @@ k_fusion_test(const DevView *__restrict__ views, int i, int con_num_thresh, floa
             if (!src_pixel(X, vs, sc, sr)) continue;
             const int sp = sr * vs.W + sc;
             if (mask_bit(vs.mask, sp)) continue;
-            const float src_depth = vs.depth[sp];
+            const float src_depth = depth_at(vs, sp);
             if (src_depth <= 0.0f) continue;
             const F3 tmp_X = world_point(sc, sr, src_depth, vs.cam);
             float tx, ty, proj_depth;
@@ -135,7 +157,7 @@ k_fusion_test(const DevView *__restrict__ views, int i, int con_num_thresh, floa
             const float reproj_error = (float)sqrt(dx * dx + dy * dy);
             const float relative_depth_diff = fabsf(proj_depth - ref_depth) / ref_depth;
             if (!(reproj_error < 2.0f && relative_depth_diff < 0.01f)) continue;
-            const float angle = get_angle(&vi.normal[(size_t)q * 3], &vs.normal[(size_t)sp * 3]);
+            const float angle = get_angle(normal_at(vi, q), normal_at(vs, sp));
             if (angle < 0.174533f) {
                 const float tmp_index = reproj_error + 200 * relative_depth_diff + angle * 10;
                 hits |= 1u << j;
@@ -173,13 +195,15 @@ k_fusion_chunks(const uint32_t *__restrict__ hit, const uint8_t *__restrict__ ap
 
 // One block. Rows 0..31: per slot the exclusive running maximum of chunk_last over the chunks (the
 // last hit before the chunk; pixel indices grow with the chunk, -1 = none). Row 32: the exclusive
-// prefix sum of chunk_count, and the view's number of points. A row is scanned in kCarrySeg
+// prefix sum of chunk_count, and the view's number of points (to view_points and / or added to the
+// running total, either may be null). A row is scanned in kCarrySeg
 // segments: each thread reduces its segment, then rescans it from what the segments before it hold.
 constexpr int kCarryThreads = (kMaxSrc + 1) * kCarrySeg;
 
 __global__ void __launch_bounds__(576)
 k_fusion_carry(int nchunks, const int *__restrict__ chunk_last, const int *__restrict__ chunk_count,
-               int *__restrict__ carry_last, int *__restrict__ chunk_base, int *__restrict__ view_points) {
+               int *__restrict__ carry_last, int *__restrict__ chunk_base, int *__restrict__ view_points,
+               long long *__restrict__ total) {
     __shared__ int seg_val[kMaxSrc + 1][kCarrySeg];
     const int tid = (int)threadIdx.x;
     const bool active = tid < kCarryThreads, counts = tid >= kMaxSrc * kCarrySeg;
@@ -205,13 +229,20 @@ k_fusion_carry(int nchunks, const int *__restrict__ chunk_last, const int *__res
             run = max(run, chunk_last[c * kMaxSrc + row]);
         }
     }
-    if (counts && seg == kCarrySeg - 1) *view_points = run;  // (the last segment ends at nchunks)
+    if (counts && seg == kCarrySeg - 1) {  // (the last segment ends at nchunks)
+        if (view_points) *view_points = run;  // the folder calls: the host places the view's points
+        if (total) {  // the in-memory fusion: the view's base is the total so far, which stays on the device
+            const long long before = total[1];
+            total[0] = before;
+            total[1] = before + run;
+        }
+    }
 }
 
 // sets the mask bit of the pixel of source slot j that pixel p of view i falls on
 __device__ inline void set_target(const DevView *views, const DevView &vi, int p, int j) {
     const int r = p / vi.W, c = p - r * vi.W;
-    const F3 X = world_point(c, r, vi.depth[p], vi.cam);
+    const F3 X = world_point(c, r, depth_at(vi, p), vi.cam);
     const DevView &vs = views[vi.src[j]];
     int sc, sr;
     if (!src_pixel(X, vs, sc, sr)) return;  // (a hit passed this very test in k_fusion_test)
@@ -219,10 +250,16 @@ __device__ inline void set_target(const DevView *views, const DevView &vi, int p
     atomicOr(&vs.mask[sp >> 5], 1u << (sp & 31));
 }
 
+// kCloud: the in-memory fusion's apply step. The approved pixel writes its whole point (world point,
+// its normal through the stride, its colour as r, g, b) into the caller's arrays at the running
+// total + its position in the view, if that lies below the capacity: no byte of a point at or
+// beyond it is written. The mask updates do not depend on the capacity. `out` is then unused.
+template <bool kCloud>
 __global__ void __launch_bounds__(kScanChunk)
 k_fusion_apply(const DevView *__restrict__ views, int i, const uint32_t *__restrict__ hit,
                const uint8_t *__restrict__ approved, const int *__restrict__ chunk_last,
-               const int *__restrict__ carry_last, const int *__restrict__ chunk_base, DevPoint *__restrict__ out) {
+               const int *__restrict__ carry_last, const int *__restrict__ chunk_base, DevPoint *__restrict__ out,
+               DevCloud cloud) {
     __shared__ uint32_t s_hit[kScanChunk];
     __shared__ int s_wave[kScanChunk / 64];
     __shared__ uint32_t s_present;  // slots with a hit somewhere in this chunk
@@ -243,8 +280,21 @@ k_fusion_apply(const DevView *__restrict__ views, int i, const uint32_t *__restr
     int pos = chunk_base[chunk] + __popcll(votes & ((1ull << lane) - 1ull));
     for (int w = 0; w < wave; ++w) pos += s_wave[w];
     const int r = q / vi.W, c = q - r * vi.W;
-    const F3 X = world_point(c, r, vi.depth[q], vi.cam);
-    out[pos] = DevPoint{X.x, X.y, X.z, (uint32_t)q};
+    const F3 X = world_point(c, r, depth_at(vi, q), vi.cam);
+    if constexpr (kCloud) {
+        const long long at = cloud.total[0] + pos;
+        if (at < cloud.capacity) {
+            const float *nrm = normal_at(vi, q);
+            float *xyz = cloud.xyz + at * 3, *normal = cloud.normal + at * 3;
+            uint8_t *rgb = cloud.rgb + at * 3;
+            xyz[0] = X.x, xyz[1] = X.y, xyz[2] = X.z;
+            normal[0] = nrm[0], normal[1] = nrm[1], normal[2] = nrm[2];
+            const uint8_t *px = vi.bgr ? vi.bgr + (size_t)q * 3 : nullptr;
+            rgb[0] = px ? px[2] : 0, rgb[1] = px ? px[1] : 0, rgb[2] = px ? px[0] : 0;
+        }
+    } else {
+        out[pos] = DevPoint{X.x, X.y, X.z, (uint32_t)q};
+    }
     const uint32_t slots = vi.nsrc >= kMaxSrc ? 0xffffffffu : (1u << vi.nsrc) - 1u;
     uint32_t need = slots & s_present;
     for (int p = tid; need && p >= 0; --p) {  // back to the chunk's start: the last hit per slot
@@ -259,7 +309,22 @@ k_fusion_apply(const DevView *__restrict__ views, int i, const uint32_t *__restr
     }
 }
 
-// ---- RunPriorAwareFusion
+// The in-memory fusion's initial mask: a view's N mask bytes (nonzero = masked) packed into its mask
+// words, one ballot per 64 pixels (wave w of the grid holds pixels 64 w .. 64 w + 63 = words 2 w and
+// 2 w + 1). N need be no multiple of 32 or 64: the bits past N are 0, and the words are allocated in
+// pairs (MaskBits' 64-bit words), so a wave that holds a pixel writes both of its words in bounds.
+__global__ void __launch_bounds__(256)
+k_mask_pack(const uint8_t *__restrict__ bytes, int N, uint32_t *__restrict__ words) {
+    const int q = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    const unsigned long long bits = __ballot(q < N && bytes[q] != 0);
+    if ((threadIdx.x & 63) == 0 && q < N) {
+        words[q >> 5] = (uint32_t)bits;
+        words[(q >> 5) + 1] = (uint32_t)(bits >> 32);
+    }
+}
+
+// ---- RunPriorAwareFusion (its kernels read a view's depth / normal as the folder calls lay them
+// out, strides 1 and 3: fuse_on_device is their only caller)
 
 // metric_of + the thresholds of get_consistency_metrics (:443-516) for one of a source's two maps:
 // whether it passes, and then exp(-index) in dc (exp's value is used nowhere else)
@@ -451,6 +516,9 @@ int fuse_on_device(Scene &sc, const JacobiCall &call, int device, Pool &pool, Cl
         v.W = sc.cols[i];
         v.H = sc.rows[i];
         v.nsrc = problems[i].num_src_images;
+        v.dstride = 1;
+        v.nstride = 3;
+        v.bgr = nullptr;  // (the colours stay with the host's collect)
         for (int j = 0; j < kMaxSrc; ++j) v.src[j] = j < v.nsrc ? sc.src_index[i][(size_t)j] : 0;
         auto put = [&](const void *src, size_t bytes) -> char * {
             char *d = arena + at;
@@ -534,13 +602,13 @@ int fuse_on_device(Scene &sc, const JacobiCall &call, int device, Pool &pool, Cl
                                                                                 d_chunk_last, d_chunk_count);
         }
         k_fusion_carry<<<1, 576, 0, hold.stream>>>(nchunks, d_chunk_last, d_chunk_count, d_carry_last, d_chunk_base,
-                                                   d_view_points + (i & 1));
+                                                   d_view_points + (i & 1), nullptr);
         if (N > 0 && prior)
             k_prior_apply<<<nchunks, kScanChunk, 0, hold.stream>>>(d_views, (int)i, d_hit, d_approved, d_chunk_base,
                                                                    d_out[i & 1]);
         else if (N > 0)
-            k_fusion_apply<<<nchunks, kScanChunk, 0, hold.stream>>>(d_views, (int)i, d_hit, d_approved, d_chunk_last,
-                                                                    d_carry_last, d_chunk_base, d_out[i & 1]);
+            k_fusion_apply<false><<<nchunks, kScanChunk, 0, hold.stream>>>(
+                d_views, (int)i, d_hit, d_approved, d_chunk_last, d_carry_last, d_chunk_base, d_out[i & 1], DevCloud{});
         FUSION_HIP_TRY(hipGetLastError());
         FUSION_HIP_TRY(hipMemcpyAsync(h_view_points + (i & 1), d_view_points + (i & 1), sizeof(int),
                                       hipMemcpyDeviceToHost, hold.stream));
@@ -570,11 +638,131 @@ int fuse_on_device(Scene &sc, const JacobiCall &call, int device, Pool &pool, Cl
     return rc;
 }
 
+// What acmmp_fuse_views_jacobi holds: its scratch on the device and in pinned host memory, freed on
+// every way out, once the caller's stream (borrowed, never destroyed) is through with it.
+struct FuseHold {
+    std::vector<void *> dev, pinned;
+    hipStream_t stream = nullptr;
+    bool pending = false;  // work is enqueued that the host has not waited for
+    ~FuseHold() {
+        if (pending) (void)hipStreamSynchronize(stream);
+        for (void *p : dev) (void)hipFree(p);
+        for (void *p : pinned) (void)hipHostFree(p);
+    }
+};
+
+// The checked views through the device on the caller's stream: mask words packed, then per view
+// test, chunks, carry (which adds the view's approvals to the running total) and apply (which writes
+// whole points at the total before the view + the position in it). No wait between views: the one
+// at the end is for the count.
+int fuse_views_on_device(int device, const acmmp_fusion_view *views, int count, float consistency_scalar,
+                         int con_num_thresh, const acmmp_cloud_buffers *out, hipStream_t stream,
+                         int64_t *num_points) {
+    const size_t n = (size_t)count;
+    FUSION_HIP_TRY(hipSetDevice(device));
+    FuseHold hold;
+    hold.stream = stream;
+    auto dev_alloc = [&](size_t bytes, void **p) -> hipError_t {
+        const hipError_t e = hipMalloc(p, std::max(bytes, size_t(256)));
+        if (e == hipSuccess) hold.dev.push_back(*p);
+        return e;
+    };
+    auto pinned_alloc = [&](size_t bytes, void **p) -> hipError_t {
+        const hipError_t e = hipHostMalloc(p, bytes, hipHostMallocDefault);
+        if (e == hipSuccess) hold.pinned.push_back(*p);
+        return e;
+    };
+    auto mask_bytes = [](size_t N) { return align256((N + 63) / 64 * sizeof(uint64_t)); };
+    size_t max_pixels = 0, mask_arena_bytes = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const size_t N = (size_t)views[i].cam.width * views[i].cam.height;
+        max_pixels = std::max(max_pixels, N);
+        mask_arena_bytes += mask_bytes(N);
+    }
+    const int max_chunks = (int)((max_pixels + kScanChunk - 1) / kScanChunk);
+    char *d_masks = nullptr;
+    DevView *d_views = nullptr, *h_views = nullptr;
+    uint32_t *d_hit = nullptr;
+    uint8_t *d_approved = nullptr;
+    int *d_chunk_last = nullptr, *d_carry_last = nullptr, *d_chunk_count = nullptr, *d_chunk_base = nullptr;
+    long long *d_total = nullptr, *h_total = nullptr;
+    FUSION_HIP_TRY(dev_alloc(mask_arena_bytes, (void **)&d_masks));
+    FUSION_HIP_TRY(dev_alloc(n * sizeof(DevView), (void **)&d_views));
+    FUSION_HIP_TRY(dev_alloc(max_pixels * sizeof(uint32_t), (void **)&d_hit));
+    FUSION_HIP_TRY(dev_alloc(max_pixels, (void **)&d_approved));
+    FUSION_HIP_TRY(dev_alloc((size_t)max_chunks * kMaxSrc * sizeof(int), (void **)&d_chunk_last));
+    FUSION_HIP_TRY(dev_alloc((size_t)max_chunks * kMaxSrc * sizeof(int), (void **)&d_carry_last));
+    FUSION_HIP_TRY(dev_alloc((size_t)max_chunks * sizeof(int), (void **)&d_chunk_count));
+    FUSION_HIP_TRY(dev_alloc((size_t)max_chunks * sizeof(int), (void **)&d_chunk_base));
+    FUSION_HIP_TRY(dev_alloc(2 * sizeof(long long), (void **)&d_total));
+    FUSION_HIP_TRY(pinned_alloc(n * sizeof(DevView), (void **)&h_views));  // pinned: the copies below do not wait
+    FUSION_HIP_TRY(pinned_alloc(sizeof(long long), (void **)&h_total));
+    size_t at = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const acmmp_fusion_view &in = views[i];
+        DevView &v = h_views[i];
+        v.cam = in.cam;
+        v.W = in.cam.width;
+        v.H = in.cam.height;
+        v.nsrc = in.num_src;
+        for (int j = 0; j < kMaxSrc; ++j) v.src[j] = j < v.nsrc ? in.src[j] : 0;
+        v.depth = in.d_depth;
+        v.normal = in.d_normal;
+        v.dstride = in.depth_stride;
+        v.nstride = in.normal_stride;
+        v.pdepth = v.pnormal = nullptr;
+        v.bgr = in.d_bgr;
+        v.mask = (uint32_t *)(d_masks + at);
+        at += mask_bytes((size_t)v.W * v.H);
+    }
+    hold.pending = true;
+    FUSION_HIP_TRY(hipMemsetAsync(d_masks, 0, mask_arena_bytes, stream));
+    FUSION_HIP_TRY(hipMemsetAsync(d_total, 0, 2 * sizeof(long long), stream));
+    FUSION_HIP_TRY(hipMemcpyAsync(d_views, h_views, n * sizeof(DevView), hipMemcpyHostToDevice, stream));
+    for (size_t i = 0; i < n; ++i) {  // every view's initial mask, before the first view's tests read a source's
+        const int N = h_views[i].W * h_views[i].H;
+        if (views[i].d_mask) k_mask_pack<<<(N + 255) / 256, 256, 0, stream>>>(views[i].d_mask, N, h_views[i].mask);
+    }
+    DevCloud cloud{};
+    if (out && out->capacity > 0) cloud = DevCloud{out->d_xyz, out->d_normal, out->d_rgb, out->capacity, nullptr};
+    cloud.total = d_total;
+    for (size_t i = 0; i < n; ++i) {
+        const int N = h_views[i].W * h_views[i].H;
+        const int nchunks = (N + kScanChunk - 1) / kScanChunk;
+        k_fusion_test<<<(N + 255) / 256, 256, 0, stream>>>(d_views, (int)i, con_num_thresh, consistency_scalar, d_hit,
+                                                           d_approved);
+        k_fusion_chunks<<<(nchunks * 32 + 255) / 256, 256, 0, stream>>>(d_hit, d_approved, N, nchunks, d_chunk_last,
+                                                                        d_chunk_count);
+        k_fusion_carry<<<1, 576, 0, stream>>>(nchunks, d_chunk_last, d_chunk_count, d_carry_last, d_chunk_base, nullptr,
+                                              d_total);
+        k_fusion_apply<true><<<nchunks, kScanChunk, 0, stream>>>(d_views, (int)i, d_hit, d_approved, d_chunk_last,
+                                                                 d_carry_last, d_chunk_base, nullptr, cloud);
+    }
+    FUSION_HIP_TRY(hipGetLastError());
+    FUSION_HIP_TRY(hipMemcpyAsync(h_total, d_total + 1, sizeof(long long), hipMemcpyDeviceToHost, stream));
+    FUSION_HIP_TRY(hipStreamSynchronize(stream));  // the call's one wait
+    hold.pending = false;
+    *num_points = *h_total;
+    if (out && out->capacity > 0 && *h_total > out->capacity)
+        return ffail(ACMMP_ERR_ARG, "the fusion produced %lld points, the cloud buffers hold %lld", *h_total,
+                     (long long)out->capacity);
+    return ACMMP_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
 int acmmp_fusion_jacobi_scan_chunk(void) { return kScanChunk; }
+
+int acmmp_fuse_views_jacobi(int device, const acmmp_fusion_view *views, int count, float consistency_scalar,
+                            int con_num_thresh, const acmmp_cloud_buffers *out, void *stream, int64_t *num_points) {
+    if (const int rc = check_fusion_views(views, count, out, num_points)) return rc;
+    *num_points = 0;
+    if (need_device("Fusing device-resident views", device)) return ACMMP_ERR_HIP;
+    return fuse_views_on_device(device, views, count, consistency_scalar, con_num_thresh, out, (hipStream_t)stream,
+                                num_points);
+}
 
 int acmmp_run_fusion_jacobi(const char *dense_folder, const char *output_folder, const acmmp_problem *problems,
                             int count, int geom_consistency, float consistency_scalar, int con_num_thresh,

@@ -7,7 +7,8 @@
 //   CacheDomain, Pool, pool_for      one L3 domain: the caller walks, workers do the rest
 //   MaskBits, Scene, FusionInputs    a fusion's inputs; masks one bit a pixel
 //   load_view .. resolve_sources     one view loader and source lookup for all fusions
-//   store_ply                        27-byte records in chunks (pool or caller)
+//   store_ply, store_ply_arrays      27-byte records in chunks (pool or caller)
+//   check_fusion_views               acmmp_fuse_views_jacobi's argument checks
 #ifndef ACMMP_FUSION_HOST_H_
 #define ACMMP_FUSION_HOST_H_
 
@@ -282,8 +283,7 @@ int pool_for(Pool &pool, int n, Fn fn) {
 
 // Float bilinear resize of an 8-bit multi-channel image (half-pixel centres,
 // edge clamp, round to nearest) — the unpinned stand-in for cv::resize.
-inline void resize_u8(const std::vector<uint8_t> &src, int sw, int sh, int C, std::vector<uint8_t> &dst, int dw, int dh) {
-    dst.resize((size_t)dw * dh * C);
+inline void resize_u8(const uint8_t *src, int sw, int sh, int C, uint8_t *dst, int dw, int dh) {
     for (int y = 0; y < dh; ++y) {
         float fy = (float)((y + 0.5) * sh / dh - 0.5);
         int y0 = (int)std::floor(fy);
@@ -307,6 +307,11 @@ inline void resize_u8(const std::vector<uint8_t> &src, int sw, int sh, int C, st
             }
         }
     }
+}
+
+inline void resize_u8(const std::vector<uint8_t> &src, int sw, int sh, int C, std::vector<uint8_t> &dst, int dw, int dh) {
+    dst.resize((size_t)dw * dh * C);
+    resize_u8(src.data(), sw, sh, C, dst.data(), dw, dh);
 }
 
 // A fusion's inputs, per view. The stages read it; walk_view alone writes (mask bits only).
@@ -445,35 +450,25 @@ inline int pwrite_all(int fd, const char *p, size_t n, off_t at) {
     return 0;
 }
 
-inline int store_ply(const std::string &path, const std::vector<Point> &pc, Pool *pool = nullptr) {
+// n records, record k formed by fill(k, o) at o: the header, then the chunks
+template <class Fill>
+int store_ply_records(const std::string &path, size_t n, Pool *pool, Fill fill) {
     char hdr[512];
     const int hl = std::snprintf(hdr, sizeof(hdr),
                                  "ply\nformat binary_little_endian 1.0\nelement vertex %d\n"
                                  "property float x\nproperty float y\nproperty float z\n"
                                  "property float nx\nproperty float ny\nproperty float nz\n"
                                  "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n",
-                                 (int)pc.size());
+                                 (int)n);
     const int fd = ::open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
     if (fd < 0) return ffail(ACMMP_ERR_IO, "cannot write %s", path.c_str());
     const size_t per = ply_chunk_points();
-    const int nchunks = (int)((pc.size() + per - 1) / per);
+    const int nchunks = (int)((n + per - 1) / per);
     auto chunk = [&](int c) -> int {
-        const size_t b = (size_t)c * per, e = std::min(pc.size(), b + per);
+        const size_t b = (size_t)c * per, e = std::min(n, b + per);
         std::vector<char> buf((e - b) * kPlyRec);
         char *o = buf.data();
-        for (size_t k = b; k < e; ++k, o += kPlyRec) {
-            const Point &p = pc[k];
-            F3 X = p.coord;
-            if (!(X.x < FLT_MAX && X.x > -FLT_MAX) || !(X.y < FLT_MAX && X.y > -FLT_MAX) ||
-                !(X.z < FLT_MAX && X.z >= -FLT_MAX)) {
-                X.x = X.y = X.z = 0.0f;
-            }
-            const float v[6] = {X.x, X.y, X.z, p.normal.x, p.normal.y, p.normal.z};
-            std::memcpy(o, v, sizeof(v));
-            o[24] = (char)(int)p.color.z;  // colour is stored b, g, r; written r, g, b
-            o[25] = (char)(int)p.color.y;
-            o[26] = (char)(int)p.color.x;
-        }
+        for (size_t k = b; k < e; ++k, o += kPlyRec) fill(k, o);
         if (pwrite_all(fd, buf.data(), buf.size(), (off_t)(hl + b * kPlyRec)))
             return ffail(ACMMP_ERR_IO, "cannot write %s", path.c_str());
         return ACMMP_OK;
@@ -483,6 +478,68 @@ inline int store_ply(const std::string &path, const std::vector<Point> &pc, Pool
     for (int c = 0; rc == ACMMP_OK && !pool && c < nchunks; ++c) rc = chunk(c);
     if (::close(fd) != 0 && rc == ACMMP_OK) rc = ffail(ACMMP_ERR_IO, "cannot write %s", path.c_str());
     return rc;
+}
+
+// a record's coordinate: one that is not finite is written as 0, 0, 0
+inline F3 ply_coord(F3 X) {
+    if (!(X.x < FLT_MAX && X.x > -FLT_MAX) || !(X.y < FLT_MAX && X.y > -FLT_MAX) ||
+        !(X.z < FLT_MAX && X.z >= -FLT_MAX)) {
+        X.x = X.y = X.z = 0.0f;
+    }
+    return X;
+}
+
+inline int store_ply(const std::string &path, const std::vector<Point> &pc, Pool *pool = nullptr) {
+    return store_ply_records(path, pc.size(), pool, [&](size_t k, char *o) {
+        const Point &p = pc[k];
+        const F3 X = ply_coord(p.coord);
+        const float v[6] = {X.x, X.y, X.z, p.normal.x, p.normal.y, p.normal.z};
+        std::memcpy(o, v, sizeof(v));
+        o[24] = (char)(int)p.color.z;  // colour is stored b, g, r; written r, g, b
+        o[25] = (char)(int)p.color.y;
+        o[26] = (char)(int)p.color.x;
+    });
+}
+
+// the same file from a cloud held as arrays (acmmp_write_ply_points): n x 3 floats, floats, bytes r, g, b
+inline int store_ply_arrays(const std::string &path, const float *xyz, const float *normal, const uint8_t *rgb,
+                            size_t n, Pool *pool = nullptr) {
+    return store_ply_records(path, n, pool, [&](size_t k, char *o) {
+        const F3 X = ply_coord(F3{xyz[k * 3], xyz[k * 3 + 1], xyz[k * 3 + 2]});
+        const float v[6] = {X.x, X.y, X.z, normal[k * 3], normal[k * 3 + 1], normal[k * 3 + 2]};
+        std::memcpy(o, v, sizeof(v));
+        std::memcpy(o + 24, rgb + k * 3, 3);
+    });
+}
+
+// acmmp_fuse_views_jacobi's arguments, all of them before any device call: ACMMP_OK or ACMMP_ERR_ARG
+// with the message. The limits are what the kernels index with: 32 source slots (a hit mask's
+// bits), source indices into views[], pixel indices below 2^27.
+inline int check_fusion_views(const acmmp_fusion_view *views, int count, const acmmp_cloud_buffers *out,
+                              const int64_t *num_points) {
+    if (count <= 0) return ffail(ACMMP_ERR_ARG, "count %d: at least one view is needed", count);
+    if (!views) return ffail(ACMMP_ERR_ARG, "null views");
+    if (!num_points) return ffail(ACMMP_ERR_ARG, "null num_points");
+    for (int i = 0; i < count; ++i) {
+        const acmmp_fusion_view &v = views[i];
+        if (v.num_src < 0 || v.num_src > 32)
+            return ffail(ACMMP_ERR_ARG, "view %d: num_src %d outside 0..32", i, v.num_src);
+        for (int j = 0; j < v.num_src; ++j)
+            if (v.src[j] < 0 || v.src[j] >= count)
+                return ffail(ACMMP_ERR_ARG, "view %d: source slot %d is view %d of %d", i, j, v.src[j], count);
+        const long long pixels = (long long)v.cam.width * v.cam.height;
+        if (v.cam.width <= 0 || v.cam.height <= 0 || pixels > (1ll << 27))
+            return ffail(ACMMP_ERR_ARG, "view %d: %d x %d maps, fusion supports 1 to 2^27 pixels", i, v.cam.width,
+                         v.cam.height);
+        if (!v.d_depth || !v.d_normal) return ffail(ACMMP_ERR_ARG, "view %d: null d_depth or d_normal", i);
+        if (v.depth_stride < 1 || v.normal_stride < 3)
+            return ffail(ACMMP_ERR_ARG, "view %d: depth_stride %lld (at least 1) or normal_stride %lld (at least 3)", i,
+                         (long long)v.depth_stride, (long long)v.normal_stride);
+    }
+    if (out && (out->capacity < 0 || (out->capacity > 0 && (!out->d_xyz || !out->d_normal || !out->d_rgb))))
+        return ffail(ACMMP_ERR_ARG, "cloud buffers: capacity %lld with a null array or below 0",
+                     (long long)out->capacity);
+    return ACMMP_OK;
 }
 
 }  // namespace acmmp_fusion_host

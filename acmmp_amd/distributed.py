@@ -311,6 +311,7 @@ class ViewParallelPipeline:
         self.mine = [v for v in self.owned if v not in self.split]  # computed whole here
         self.state = {}     # own views: problem index -> ViewResult (latest pass)
         self.depths = {}    # every view: problem index -> depth tensor view (previous pass, gathered)
+        self._ran = False   # run() finished: self.state holds every view's final maps (fuse())
         self.pass_index = 0
         self.pass_log = []  # per pass: kind and wall seconds of its phases (tools/scale_sim.py)
 
@@ -620,7 +621,64 @@ class ViewParallelPipeline:
             self._shutdown()
         if dist.is_initialized() and self.world > 1:
             dist.barrier(group=self.group)
+        self._ran = True
         return self.output_folder
+
+    # ------------------------------------------------------------- fusion
+    def fuse(self, consistency_scalar: float = 0.3, num_consistent_thresh: int = 1, mask_dir: Optional[str] = None,
+             ply: bool = True):
+        """RunFusion in Jacobi order over the last pass's maps where they lie,
+        in HBM (fusion.fuse_views; no .dmb is read back): after run(), at
+        world size 1. The views are self.state[v].planes with the last
+        scale's cameras; the colours are decoded from <dense>/images (resized
+        only where an image's size differs from its maps'), the optional masks
+        <dense>/<mask_dir>/%08d.png prepared as RunFusion prepares them.
+        Returns (xyz, normal, rgb) as device tensors, the points
+        `pipeline.run_fusion(order="jacobi")` writes for the folder this run
+        wrote, in its order; ply=True also writes <output>/ACMMP_model.ply."""
+        from . import fusion
+        if self.world > 1:
+            raise AcmmpError("fuse() fuses the maps resident on one rank; at world size "
+                             f"{self.world} use pipeline.run_fusion on the output folder")
+        if not self._ran or len(self.state) != len(self.problems):
+            raise AcmmpError("fuse() needs the maps of a finished run(): call run() first")
+        if self.tdev.type != "cuda":
+            raise AcmmpError("fuse() needs the maps on a HIP device")
+
+        def host_inputs(v):  # on a pool thread: the decoders drop the GIL
+            p = self.problems[v]
+            H, W = self.state[v].planes.shape[:2]
+            bgr = aio.read_image_bgr(os.path.join(self.dense, "images", "%08d.jpg" % p.ref_image_id))
+            if bgr.shape[:2] != (H, W):
+                bgr = fusion.resize_bilinear_u8(bgr, W, H)
+            mask = None
+            if mask_dir is not None:
+                mask = fusion.initial_mask(os.path.join(self.dense, mask_dir, "%08d.png" % p.ref_image_id), W, H)
+            return bgr, mask
+
+        from concurrent.futures import ThreadPoolExecutor
+        order = list(range(len(self.problems)))
+        with self._timed("fuse_decode"):
+            workers = max(1, min(_abi.load_library().acmmp_host_threads(), len(order)))
+            with ThreadPoolExecutor(max_workers=workers) as ex:
+                host = list(ex.map(host_inputs, order))
+        with self._timed("fuse_upload"):  # colours and masks only: the maps are where the passes left them
+            views = []
+            for v, (bgr, mask) in zip(order, host):
+                p = self.problems[v]
+                views.append(fusion.FusionView.from_planes(
+                    self.state[v].planes, self.cams[p.ref_image_id], [self.index_of[s] for s in p.sources],
+                    bgr=torch.from_numpy(bgr).to(self.tdev),
+                    mask=None if mask is None else torch.from_numpy(mask).to(self.tdev)))
+            self._sync()
+        with self._timed("fuse_device"):  # enqueue + the call's one wait
+            cloud = fusion.fuse_views(views, consistency_scalar, num_consistent_thresh, device=self.device)
+        if ply:
+            with self._timed("fuse_download"):
+                host_cloud = [t.cpu() for t in cloud]
+            with self._timed("fuse_ply"):
+                fusion.write_ply(os.path.join(self.output_folder, "ACMMP_model.ply"), *host_cloud)
+        return cloud
 
 
 def main():
@@ -638,6 +696,9 @@ def main():
     ap.add_argument("--backend", default=None, help="nccl (RCCL, default with GPUs) or gloo")
     ap.add_argument("--concurrent_views", type=int, default=2,
                     help="views computed at once per GPU (one engine / HIP stream each)")
+    ap.add_argument("--fuse", action="store_true",
+                    help="then fuse the resident maps into <output>/ACMMP_model.ply (RunFusion in Jacobi order; "
+                         "one process only)")
     args = ap.parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -652,6 +713,9 @@ def main():
     out = pipe.run()
     if pipe.rank == 0:
         print(f"Depth/normal/cost maps written under {out}")
+    if args.fuse:
+        xyz, _, _ = pipe.fuse()
+        print(f"{len(xyz)} points written to {os.path.join(out, 'ACMMP_model.ply')}")
     if dist.is_initialized():
         dist.destroy_process_group()
 

@@ -559,7 +559,71 @@ int acmmp_run_prior_aware_fusion_jacobi(const char *dense_folder, const char *ou
                                         const char *fusion_folder, const acmmp_problem *problems, int count,
                                         int geom_consistency, float consistency_scalar, int num_consistent_thresh,
                                         int single_match_penalty, int device, int *num_points);
-/* Message of the last failing acmmp_run_fusion / _prior_aware_fusion (either order) on this thread. */
+/* One view of acmmp_fuse_views_jacobi: its camera, sources and maps, all in
+ * device memory. Depth and normal are read through strides, so a view can be
+ * a depth plane plus a normal map (strides 1 / 3, the .dmb layout) or one
+ * H x W float4 planes tensor (normal xyz + depth: d_normal = planes,
+ * d_depth = planes + 3, strides 4 / 4), which is what acmmp_export_results
+ * leaves on the device. */
+typedef struct acmmp_fusion_view {
+    acmmp_camera cam;            /* at the maps' size; cam.width/height are the maps' W, H */
+    int32_t num_src;             /* 0..32 */
+    int32_t src[32];             /* indices into views[] (a view may list itself) */
+    const float *d_depth;        /* device; pixel q's depth at d_depth[q * depth_stride] */
+    int64_t depth_stride;        /* in floats: 1 for a depth plane, 4 for the .w of float4 planes */
+    const float *d_normal;       /* device; pixel q's world normal at d_normal[q * normal_stride + 0..2] */
+    int64_t normal_stride;       /* 3 for a normal map, 4 for float4 planes */
+    const uint8_t *d_bgr;        /* device, H*W*3 in B,G,R; NULL: colour 0,0,0 */
+    const uint8_t *d_mask;       /* device, H*W bytes, nonzero = masked before view 0; NULL: none */
+} acmmp_fusion_view;
+
+/* Where acmmp_fuse_views_jacobi leaves the cloud: three device arrays of
+ * `capacity` points each, the caller's. */
+typedef struct acmmp_cloud_buffers {
+    float *d_xyz;                /* device, capacity*3 floats */
+    float *d_normal;             /* device, capacity*3 floats */
+    uint8_t *d_rgb;              /* device, capacity*3 bytes, R,G,B as the PLY stores them */
+    int64_t capacity;            /* points the three arrays hold */
+} acmmp_cloud_buffers;
+
+/* acmmp_run_fusion_jacobi's rule over views that already lie
+ * in device memory, the cloud left on the device: point k of `out` is the
+ * point the folder call puts k-th in its PLY for the same maps, cameras,
+ * sources, colours and initial masks (view order, then pixel order). d_xyz
+ * holds the world point as computed (acmmp_write_ply_points zeroes a
+ * non-finite one, as the folder call's writer), d_normal the pixel's normal,
+ * d_rgb its colour as r, g, b. Views may differ in size; no input is written.
+ * Everything (the packing of the byte masks into the kernels' mask words, and
+ * per view the test, scan and apply kernels) is enqueued on `stream` (a
+ * hipStream_t; NULL = the legacy default stream); the views' output bases are
+ * a running total kept on the device, and the host waits once, at the end,
+ * for the count. *num_points always receives the number of points the fusion
+ * produced: if it exceeds out->capacity the call returns ACMMP_ERR_ARG (the
+ * message names both numbers) and nothing at or beyond `capacity` points has
+ * been written in any array (the position is checked in the kernel); the
+ * first `capacity` points are the full run's. out == NULL or capacity == 0
+ * only counts. Checked on the host before any device call, ACMMP_ERR_ARG
+ * (acmmp_fusion_last_error): count <= 0, null views or num_points, num_src
+ * outside 0..32, a source index outside [0, count), W * H outside (0, 2^27],
+ * null d_depth / d_normal, depth_stride < 1, normal_stride < 3, a capacity
+ * below 0 or above 0 with a null array. Then, without a usable device,
+ * ACMMP_ERR_HIP. Scratch (mask words, hit masks, flags, scan rows) is the
+ * call's own and freed on every way out. */
+int acmmp_fuse_views_jacobi(int device, const acmmp_fusion_view *views, int count, float consistency_scalar,
+                            int con_num_thresh, const acmmp_cloud_buffers *out, void *stream, int64_t *num_points);
+/* StoreColorPlyFileBinaryPointCloud (src/ACMMP.cpp:382-424) over host arrays
+ * of n points (xyz, normal: n*3 floats; rgb: n*3 bytes r, g, b): the file
+ * acmmp_run_fusion writes for the same cloud, a point with a coordinate that
+ * is not finite written as 0, 0, 0. n == 0 writes the header alone (the
+ * arrays may then be null). */
+int acmmp_write_ply_points(const char *path, const float *xyz, const float *normal, const uint8_t *rgb, int64_t n);
+/* The fusions' stand-in for cv::resize on 8-bit images: float
+ * bilinear, half-pixel centres, edge clamp, round to nearest; src sh x sw x
+ * channels, dst dh x dw x channels (channels 1..4). What the fusion calls
+ * apply to an image or mask whose size differs from the maps'. */
+int acmmp_resize_bilinear_u8(const uint8_t *src, int sw, int sh, int channels, uint8_t *dst, int dw, int dh);
+/* Message of the last failing acmmp_run_fusion / _prior_aware_fusion (either order), acmmp_fuse_views_jacobi,
+ * acmmp_write_ply_points or acmmp_resize_bilinear_u8 on this thread. */
 const char *acmmp_fusion_last_error(void);
 
 /* Message of the last failing driver call on this thread ("" when none). */
