@@ -14,8 +14,8 @@
 //
 // What the Jacobi-order device fusion (acmmp_fusion_dev.hip) needs as well lives in
 // acmmp_fusion_host.h: world_point / project, CacheDomain, Pool, pool_for, MaskBits, Scene,
-// FusionInputs, load_view .. resolve_sources, store_ply, the error string. This file builds
-// without HIP.
+// FusionInputs, the loaders (load_view .. load_prior_view: both orders of a fusion load the same
+// way), check_view_sizes, store_ply, the error string. This file builds without HIP.
 //
 // The file, in order (RunFusion unless said otherwise):
 //   get_angle .. stage_reproject     the reference's float expressions, vectorised stages
@@ -440,9 +440,6 @@ int acmmp_run_fusion(const char *dense_folder, const char *output_folder, const 
                      const char *mask_folder, int write_debug_images, int *num_points) {
     if (!dense_folder || !output_folder || !problems || count <= 0) return ffail(ACMMP_ERR_ARG, "bad args");
     const std::string dense = dense_folder, out = output_folder;
-    const std::string image_folder = dense + (image_dir ? image_dir : "/images");
-    const bool use_masks = mask_folder && std::string(mask_folder) != " " && mask_folder[0] != 0;
-    const char *suffix = geom_consistency ? "/depths_geom.dmb" : "/depths.dmb";
     const size_t n = (size_t)count;
     const bool timing = std::getenv("ACMMP_HOST_TIMING") != nullptr;
     const auto t_start = Clock::now();
@@ -453,23 +450,9 @@ int acmmp_run_fusion(const char *dense_folder, const char *output_folder, const 
     // lay on the other node: walk 0.85 or 1.3 s from run to run, profiles/r05_fusion_walk_ab3.jsonl.)
     CacheDomain dom;
     Pool pool(&dom);
-    // views load independently (JPEG decode, two .dmb reads, optional mask)
-    int rc = pool_for(pool, (int)n, [&](int vi) -> int {
-        const size_t i = (size_t)vi;
-        const int id = problems[i].ref_image_id;
-        const int load_rc = load_view(sc, i, image_folder, dense, result_folder(out, id), suffix);
-        if (load_rc) return load_rc;
-        sc.masks[i].assign((size_t)sc.cols[i] * sc.rows[i]);
-        if (!use_masks) return (int)ACMMP_OK;
-        return load_initial_mask(dense + "/" + mask_folder + "/" + id8(id) + ".png", sc.cols[i], sc.rows[i],
-                                 sc.masks[i]);
-    });
-    if (!rc) rc = resolve_sources(sc);
+    int rc = load_fusion_views(sc, pool, dense_folder, output_folder, geom_consistency, image_dir, mask_folder);
+    if (!rc) rc = check_view_sizes(sc);  // (a hit packs the pixel in kSpBits = 27 bits, the slot in 5)
     if (rc) return rc;
-    for (size_t i = 0; i < n; ++i)
-        if ((size_t)sc.cols[i] * sc.rows[i] > (size_t(1) << kSpBits) || problems[i].num_src_images > 32)
-            return ffail(ACMMP_ERR_ARG, "view %d: fusion supports images up to 2^27 pixels and 32 sources",
-                         problems[i].ref_image_id);
     std::vector<Point> cloud;  // reserved once (pages are committed as points arrive): no copies in the walk
     cloud.reserve(sc.pixels());
     ViewHits vhits[2];
@@ -516,18 +499,9 @@ int acmmp_run_prior_aware_fusion(const char *dense_folder, const char *output_fo
     const size_t n = (size_t)count;
     FusionInputs in(problems, n);
     std::vector<std::vector<uint8_t>> &images = in.images, masks(n);
-    const char *suffix = geom_consistency ? "/depths_geom.dmb" : "/depths.dmb";
-    for (size_t i = 0; i < n; ++i) {
-        const int id = problems[i].ref_image_id;
-        // maps of the other reconstruction (fusion_folder) and of this run's (output_folder) priors
-        int rc = load_view(in, i, dense + "/images", dense, result_folder(fus, id), suffix);
-        int h = 0, w = 0;
-        if (!rc) rc = read_maps(result_folder(out, id), suffix, id, in.pdepths[i], in.pnormals[i], h, w);
-        if (rc) return rc;
-        if (h != in.rows[i] || w != in.cols[i]) return ffail(ACMMP_ERR_IO, "map sizes of view %d disagree", id);
-        // mask files give 255/0 here (:654-661), never the 1 the checks test:
-        // only approvals mask pixels
-        masks[i].assign((size_t)w * h, 0);
+    for (size_t i = 0; i < n; ++i) {  // one after the other, on the calling thread
+        if (const int rc = load_prior_view(in, i, dense, out, fus, depth_suffix(geom_consistency))) return rc;
+        masks[i].assign((size_t)in.cols[i] * in.rows[i], 0);
     }
     const int src_rc = resolve_sources(in);
     if (src_rc) return src_rc;

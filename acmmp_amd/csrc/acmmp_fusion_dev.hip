@@ -1,55 +1,50 @@
-// acmmp_fusion_dev.hip — the two fusions in Jacobi order on the device: RunFusion
-// (src/acmmp_definitions.cpp:828-1043) as acmmp_run_fusion_jacobi, RunPriorAwareFusion (:573-826) as
-// acmmp_run_prior_aware_fusion_jacobi (after RunFusion's kernels below).
-// RunFusion: the literal fusion (acmmp_fusion.cpp) walks a view's pixels one after the other
-// because an approval masks source pixels that later pixels of the SAME view then skip. Here
-// every pixel of view i reads the masks as they stood before view i's first pixel (its
-// own mask bit and every source's, also when a view lists itself as a source); view i's mask writes
-// become visible to view i + 1. Nothing else changes: view order, pixel order, the float
-// expressions (world_point / project of acmmp_fusion_host.h, shared with the host), the thresholds,
-// and used_list, which the reference never resets between pixels. A view is then three
-// data-parallel steps on one stream:
-//   k_fusion_test    a thread a pixel: per source slot the reference's tests against the masks as
-//                    they stand (nothing writes them meanwhile); out: the pixel's 32-bit hit mask
-//                    (bit j = source slot j passed) and its approval flag
-//   k_fusion_chunks  per chunk of kScanChunk pixels and slot: the chunk's last hit; per chunk: its
-//   k_fusion_carry   approvals. Then across chunks: the last hit before each chunk per slot, and
-//                    the exclusive prefix of the approvals (the points' positions)
-//   k_fusion_apply   a block a chunk: an approved pixel writes its point at its position and, per
-//                    slot, sets the mask bit of the target of the last hit at or before it (that is
-//                    used_list: an unapproved pixel's hit is applied by the next approval unless a
-//                    later hit on the same slot replaced it). Targets are not stored: recomputed by
-//                    the expression the test used. Atomic ORs of single bits: any thread order
-//                    gives the same masks.
-// libm: acos / exp are the project's pinned dm_acosf / dm_expf (the literal fusion calls the
-// host's libm): same bits on host, device and in the tests' restatement. dm_acosf is NaN outside
+// acmmp_fusion_dev.hip — fusion in Jacobi order on the device: one rule for a view, three carriers.
+//
+// The rule. The literal fusions (acmmp_fusion.cpp) walk a view's pixels one after the other because
+// an approval masks source pixels that later pixels of the SAME view then skip. Here every pixel of
+// view i reads the masks as they stood before view i's first pixel (its own mask bit and every
+// source's, also when a view lists itself as a source); view i's mask writes become visible to view
+// i + 1. Nothing else changes: view order, pixel order, the thresholds, the float expressions
+// (world_point / project of acmmp_fusion_host.h, shared with the host). A view is then four
+// data-parallel launches on one stream (enqueue_view):
+//   test     a thread a pixel: per source slot the reference's tests against the masks
+//            as they stand (nothing writes them meanwhile); out: the pixel's 32-bit hit mask (bit j
+//            = source slot j passed) and its flag byte (approved, and what the carrier adds)
+//   chunks   per chunk of kScanChunk pixels and slot: the chunk's last hit; per chunk: its approvals.
+//   carry    Then across chunks: the last hit before each chunk per slot, and the exclusive prefix
+//            of the approvals (the points' positions)
+//   apply    its own launch after the test (fused, one pixel's write could reach another pixel's
+//            test of the same view), a block a chunk: an approved pixel writes its point at its
+//            position and sets mask bits of source pixels. Targets are not stored: recomputed by
+//            the expression the test used. Atomic ORs of single bits: any thread order is the same.
+// libm: acos / exp are the project's pinned dm_acosf / dm_expf (the literal fusions call the
+// host's libm): same bits on host, device and in the tests' restatements. dm_acosf is NaN outside
 // [-1, 1], so GetAngle's "NaN -> 0" gives angle 0 for a dot product just above 1.
 // int(p + 0.5f): the host's conversion of a NaN, an infinity or a value outside int is INT_MIN,
-// which the bounds test rejects; the device's saturates (NaN -> 0, in bounds). src_pixel tests the
+// which the bounds test rejects; the device's saturates (NaN -> 0, in bounds). pixel_coord tests the
 // range before converting: not finite or outside [-2^31, 2^31) is out of bounds.
 //
-// RunPriorAwareFusion has no used_list (declared at :679, never used): an approved pixel masks the
-// targets of its own chosen hypothesis's below-threshold candidates (:814-818) and nothing else, so
-// there are no stale entries and no last-hit rows. A view is
-//   k_prior_test     a thread a pixel: both hypotheses (0 = fusion_folder's maps, 1 = output_folder's,
-//                    this run's priors) against both maps of every source, the choice (:754-789);
-//                    out: the chosen hypothesis's 32-bit hit mask and a flag byte (bit 0 approved,
-//                    bit 1 the chosen hypothesis)
-//   k_fusion_chunks  the approvals' exclusive prefix, as above (the last-hit rows it also fills are
-//   k_fusion_carry   not read)
-//   k_prior_apply    its own launch after the test (fused, one pixel's write could reach another
-//                    pixel's test of the same view): an approved pixel writes its point at its
-//                    position (the chosen hypothesis in bit 31 of the pixel index) and sets the mask
-//                    bit of every hit's target, recomputed by the test's expression
-// Both calls share the host side (fuse_on_device): one upload of every view's maps, one stream,
-// view i's points copied back and collected while view i + 1's kernels run.
-//
-// acmmp_fuse_views_jacobi is RunFusion's rule over views that already lie in device memory
-// (fuse_views_on_device): depth and normal read through strides (a float4 planes tensor serves as
-// both), byte masks packed by k_mask_pack, the same test / chunks / carry kernels, and
-// k_fusion_apply<true>, which writes whole points (xyz, normal, r g b) into the caller's arrays at
-// the running total k_fusion_carry keeps on the device + the position in the view, guarded by the
-// arrays' capacity. All on the caller's stream, no wait between views, one at the end for the count.
+// The carriers, and what each differs in:
+//   acmmp_run_fusion_jacobi (RunFusion, src/acmmp_definitions.cpp:828-1043): k_fusion_test, and
+//     k_fusion_apply<false>, which per slot sets the mask bit of the target of the last hit at or
+//     before the approved pixel. That is used_list, which the reference never resets between
+//     pixels: an unapproved pixel's hit is applied by the next approval unless a later hit on the
+//     same slot replaced it.
+//   acmmp_run_prior_aware_fusion_jacobi (RunPriorAwareFusion, :573-826): k_prior_test, both
+//     hypotheses (0 = fusion_folder's maps, 1 = output_folder's, this run's priors) against both
+//     maps of every source and the choice (:754-789); the hit mask is the chosen hypothesis's, the
+//     flag byte and bit 31 of the point's pixel index name it. No used_list (declared at :679, never
+//     used): in k_prior_apply an approved pixel masks the targets of its own hits (:814-818) and
+//     nothing else, so the last-hit rows of chunks / carry are not read.
+//   Both are folder calls (fuse_on_device): one upload of every view's maps, a stream of its own,
+//     view i's 16-byte points copied back and collected (normal, colour: the host's) while view
+//     i + 1's kernels run.
+//   acmmp_fuse_views_jacobi (fuse_views_on_device): RunFusion's rule over views that already lie in
+//     device memory: depth and normal read through strides (a float4 planes tensor serves as both),
+//     byte masks packed by k_mask_pack, and k_fusion_apply<true>, which writes whole points (xyz,
+//     normal, r g b) into the caller's arrays at the running total k_fusion_carry keeps on the
+//     device + the position in the view, below the arrays' capacity. All on the caller's stream, no
+//     wait between views, one at the end for the count.
 #include <hip/hip_runtime.h>
 
 #include "acmmp_fusion_host.h"
@@ -429,27 +424,115 @@ k_prior_apply(const DevView *__restrict__ views, int i, const uint32_t *__restri
 using Clock = std::chrono::steady_clock;
 double secs(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double>(b - a).count(); }
 
-// what the call holds on the device and in pinned host memory: released on every way out
-struct DevHold {
-    std::vector<void *> dev, pinned;
-    hipStream_t stream = nullptr;
-    hipEvent_t copied[2] = {nullptr, nullptr};
-    ~DevHold() {
-        if (stream) (void)hipStreamSynchronize(stream);
-        for (hipEvent_t e : copied)
-            if (e) (void)hipEventDestroy(e);
-        for (void *p : dev) (void)hipFree(p);
-        for (void *p : pinned) (void)hipHostFree(p);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-};
-
 #define FUSION_HIP_TRY(expr)                                                                               \
     do {                                                                                                   \
         const hipError_t e_ = (expr);                                                                      \
         if (e_ != hipSuccess)                                                                              \
             return ffail(ACMMP_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
+
+// What a call holds on the device and in pinned host memory, released on every way out: the stream
+// drained, then the events, the memory, and the stream if it is the call's own. A caller's stream
+// (borrowed: set `stream` and leave `owned`) is never destroyed, and waited for only while `pending`.
+struct DevHold {
+    std::vector<void *> dev, pinned;
+    hipStream_t stream = nullptr;
+    bool owned = false;    // created by own_stream
+    bool pending = false;  // work is enqueued that the host has not waited for
+    hipEvent_t copied[2] = {nullptr, nullptr};  // optional
+    ~DevHold() {
+        if (pending) (void)hipStreamSynchronize(stream);
+        for (hipEvent_t e : copied)
+            if (e) (void)hipEventDestroy(e);
+        for (void *p : dev) (void)hipFree(p);
+        for (void *p : pinned) (void)hipHostFree(p);
+        if (owned) (void)hipStreamDestroy(stream);
+    }
+    hipError_t own_stream() {
+        const hipError_t e = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
+        owned = pending = e == hipSuccess;  // (pending for good: every way out drains it)
+        return e;
+    }
+    template <class T>
+    hipError_t dev_alloc(T *&p, size_t count) {
+        const hipError_t e = hipMalloc((void **)&p, std::max(count * sizeof(T), size_t(256)));
+        if (e == hipSuccess) dev.push_back(p);
+        return e;
+    }
+    template <class T>
+    hipError_t pinned_alloc(T *&p, size_t count) {
+        const hipError_t e = hipHostMalloc((void **)&p, count * sizeof(T), hipHostMallocDefault);
+        if (e == hipSuccess) pinned.push_back(p);
+        return e;
+    }
+};
+
+// what a view's launches hand to each other, sized for the call's largest view
+struct ViewScratch {
+    uint32_t *hit = nullptr;                            // [pixel]: its hit mask
+    uint8_t *flag = nullptr;                            // [pixel]: its flag byte
+    int *chunk_last = nullptr, *carry_last = nullptr;   // [chunk][slot]
+    int *chunk_count = nullptr, *chunk_base = nullptr;  // [chunk]
+};
+
+int alloc_scratch(DevHold &hold, size_t max_pixels, ViewScratch &s) {
+    const size_t max_chunks = (max_pixels + kScanChunk - 1) / kScanChunk;
+    FUSION_HIP_TRY(hold.dev_alloc(s.hit, max_pixels));
+    FUSION_HIP_TRY(hold.dev_alloc(s.flag, max_pixels));
+    FUSION_HIP_TRY(hold.dev_alloc(s.chunk_last, max_chunks * kMaxSrc));
+    FUSION_HIP_TRY(hold.dev_alloc(s.carry_last, max_chunks * kMaxSrc));
+    FUSION_HIP_TRY(hold.dev_alloc(s.chunk_count, max_chunks));
+    FUSION_HIP_TRY(hold.dev_alloc(s.chunk_base, max_chunks));
+    return ACMMP_OK;
+}
+
+// a view's table entry but for what the carriers differ in: the pointers, strides, bgr and the
+// prior pair (null here)
+DevView dev_view(const acmmp_camera &cam, int W, int H, const int *src, int nsrc) {
+    DevView v{cam, W, H, nsrc};  // (the other slots 0, the pointers null)
+    for (int j = 0; j < nsrc; ++j) v.src[j] = src[j];
+    return v;
+}
+
+// what the carriers' tests differ in
+struct JacobiRule {
+    bool prior;  // RunPriorAwareFusion's test and apply step, else RunFusion's
+    float consistency_scalar;
+    int num_consistent_thresh, single_match_penalty;
+};
+
+// View i's (N pixels) launches on the stream: test, chunks, carry, apply. The caller passes one of
+// two pairs and leaves the other null / empty, and that picks the apply step: `out` (16-byte
+// points) with `view_points` (the carry writes the view's count there): the folder calls,
+// k_prior_apply if rule.prior, else k_fusion_apply<false>; or `cloud` (whole points) with `total`
+// (the carry adds to the running total): the in-memory call, k_fusion_apply<true>, never with
+// rule.prior. A view without pixels (the folder calls only) gets the carry alone: its count is 0.
+void enqueue_view(hipStream_t stream, const DevView *d_views, int i, int N, const ViewScratch &s,
+                  const JacobiRule &rule, DevPoint *out, const DevCloud &cloud, int *view_points, long long *total) {
+    const int nchunks = (N + kScanChunk - 1) / kScanChunk;
+    if (N > 0) {
+        if (rule.prior)
+            k_prior_test<<<(N + 255) / 256, 256, 0, stream>>>(d_views, i, rule.num_consistent_thresh,
+                                                              rule.single_match_penalty, rule.consistency_scalar,
+                                                              s.hit, s.flag);
+        else
+            k_fusion_test<<<(N + 255) / 256, 256, 0, stream>>>(d_views, i, rule.num_consistent_thresh,
+                                                               rule.consistency_scalar, s.hit, s.flag);
+        k_fusion_chunks<<<(nchunks * 32 + 255) / 256, 256, 0, stream>>>(s.hit, s.flag, N, nchunks, s.chunk_last,
+                                                                        s.chunk_count);
+    }
+    k_fusion_carry<<<1, 576, 0, stream>>>(nchunks, s.chunk_last, s.chunk_count, s.carry_last, s.chunk_base,
+                                          view_points, total);
+    if (N <= 0) return;
+    if (rule.prior)
+        k_prior_apply<<<nchunks, kScanChunk, 0, stream>>>(d_views, i, s.hit, s.flag, s.chunk_base, out);
+    else if (out)
+        k_fusion_apply<false><<<nchunks, kScanChunk, 0, stream>>>(d_views, i, s.hit, s.flag, s.chunk_last,
+                                                                  s.carry_last, s.chunk_base, out, DevCloud{});
+    else
+        k_fusion_apply<true><<<nchunks, kScanChunk, 0, stream>>>(d_views, i, s.hit, s.flag, s.chunk_last,
+                                                                 s.carry_last, s.chunk_base, nullptr, cloud);
+}
 
 size_t align256(size_t n) { return (n + 255) / 256 * 256; }
 
@@ -463,11 +546,10 @@ int need_device(const char *what, int device) {
     return ACMMP_OK;
 }
 
-// what the two calls differ in once their views are loaded
+// what the two folder calls differ in once their views are loaded
 struct JacobiCall {
+    JacobiRule rule;
     const std::vector<std::vector<float>> *pdepths, *pnormals;  // the prior-aware fusion's second pair, else null
-    float consistency_scalar;
-    int num_consistent_thresh, single_match_penalty;
     const char *tag;  // of the ACMMP_HOST_TIMING line
     std::string ply;
 };
@@ -477,28 +559,19 @@ int fuse_on_device(Scene &sc, const JacobiCall &call, int device, Pool &pool, Cl
                    int *num_points) {
     const acmmp_problem *problems = sc.problems;
     const size_t n = sc.rows.size();
-    const bool prior = call.pdepths != nullptr;
+    const bool prior = call.rule.prior;
     const bool timing = std::getenv("ACMMP_HOST_TIMING") != nullptr;
-    int rc = ACMMP_OK;
+    int rc = check_view_sizes(sc);
+    if (rc) return rc;
     size_t max_pixels = 0;
-    for (size_t i = 0; i < n; ++i) {
-        if ((size_t)sc.cols[i] * sc.rows[i] > (size_t(1) << 27) || problems[i].num_src_images > kMaxSrc)
-            return ffail(ACMMP_ERR_ARG, "view %d: fusion supports images up to 2^27 pixels and 32 sources",
-                         problems[i].ref_image_id);
-        max_pixels = std::max(max_pixels, (size_t)sc.cols[i] * sc.rows[i]);
-    }
+    for (size_t i = 0; i < n; ++i) max_pixels = std::max(max_pixels, (size_t)sc.cols[i] * sc.rows[i]);
     const auto t_loaded = Clock::now();
 
     // ---- upload: every view's depth, normal and mask words, and the table of views, once
     FUSION_HIP_TRY(hipSetDevice(device));
     DevHold hold;
-    FUSION_HIP_TRY(hipStreamCreateWithFlags(&hold.stream, hipStreamNonBlocking));
+    FUSION_HIP_TRY(hold.own_stream());
     for (hipEvent_t &e : hold.copied) FUSION_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    auto dev_alloc = [&](size_t bytes, void **p) -> hipError_t {
-        const hipError_t e = hipMalloc(p, std::max(bytes, size_t(256)));
-        if (e == hipSuccess) hold.dev.push_back(*p);
-        return e;
-    };
     size_t arena_bytes = 0;
     for (size_t i = 0; i < n; ++i) {
         const size_t N = (size_t)sc.cols[i] * sc.rows[i];
@@ -506,20 +579,15 @@ int fuse_on_device(Scene &sc, const JacobiCall &call, int device, Pool &pool, Cl
                        align256(sc.masks[i].w.size() * sizeof(uint64_t));
     }
     char *arena = nullptr;
-    FUSION_HIP_TRY(dev_alloc(arena_bytes, (void **)&arena));
+    FUSION_HIP_TRY(hold.dev_alloc(arena, arena_bytes));
     std::vector<DevView> views(n);
     size_t at = 0;
     for (size_t i = 0; i < n; ++i) {
         const size_t N = (size_t)sc.cols[i] * sc.rows[i];
         DevView &v = views[i];
-        v.cam = sc.cameras[i];
-        v.W = sc.cols[i];
-        v.H = sc.rows[i];
-        v.nsrc = problems[i].num_src_images;
+        v = dev_view(sc.cameras[i], sc.cols[i], sc.rows[i], sc.src_index[i].data(), problems[i].num_src_images);
         v.dstride = 1;
-        v.nstride = 3;
-        v.bgr = nullptr;  // (the colours stay with the host's collect)
-        for (int j = 0; j < kMaxSrc; ++j) v.src[j] = j < v.nsrc ? sc.src_index[i][(size_t)j] : 0;
+        v.nstride = 3;  // (bgr stays null: the colours stay with the host's collect)
         auto put = [&](const void *src, size_t bytes) -> char * {
             char *d = arena + at;
             at += align256(bytes);
@@ -535,29 +603,17 @@ int fuse_on_device(Scene &sc, const JacobiCall &call, int device, Pool &pool, Cl
                          hipGetErrorString(hipGetLastError()));
     }
     DevView *d_views = nullptr;
-    FUSION_HIP_TRY(dev_alloc(n * sizeof(DevView), (void **)&d_views));
+    FUSION_HIP_TRY(hold.dev_alloc(d_views, n));
     FUSION_HIP_TRY(hipMemcpyAsync(d_views, views.data(), n * sizeof(DevView), hipMemcpyHostToDevice, hold.stream));
-    // per-view scratch, sized for the largest view
-    const int max_chunks = (int)((max_pixels + kScanChunk - 1) / kScanChunk);
-    uint32_t *d_hit = nullptr;
-    uint8_t *d_approved = nullptr;
-    int *d_chunk_last = nullptr, *d_carry_last = nullptr, *d_chunk_count = nullptr, *d_chunk_base = nullptr;
-    int *d_view_points = nullptr, *h_view_points = nullptr;
+    ViewScratch scratch;
+    if ((rc = alloc_scratch(hold, max_pixels, scratch))) return rc;
+    int *d_view_points = nullptr, *h_view_points = nullptr;  // [i & 1], as the points: view i's count
     DevPoint *d_out[2] = {nullptr, nullptr}, *h_out[2] = {nullptr, nullptr};
-    FUSION_HIP_TRY(dev_alloc(max_pixels * sizeof(uint32_t), (void **)&d_hit));
-    FUSION_HIP_TRY(dev_alloc(max_pixels, (void **)&d_approved));
-    FUSION_HIP_TRY(dev_alloc((size_t)max_chunks * kMaxSrc * sizeof(int), (void **)&d_chunk_last));
-    FUSION_HIP_TRY(dev_alloc((size_t)max_chunks * kMaxSrc * sizeof(int), (void **)&d_carry_last));
-    FUSION_HIP_TRY(dev_alloc((size_t)max_chunks * sizeof(int), (void **)&d_chunk_count));
-    FUSION_HIP_TRY(dev_alloc((size_t)max_chunks * sizeof(int), (void **)&d_chunk_base));
-    FUSION_HIP_TRY(dev_alloc(2 * sizeof(int), (void **)&d_view_points));
-    FUSION_HIP_TRY(hipHostMalloc((void **)&h_view_points, 2 * sizeof(int), hipHostMallocDefault));
-    hold.pinned.push_back(h_view_points);
+    FUSION_HIP_TRY(hold.dev_alloc(d_view_points, 2));
+    FUSION_HIP_TRY(hold.pinned_alloc(h_view_points, 2));
     for (int b = 0; b < 2; ++b) {
-        FUSION_HIP_TRY(dev_alloc(max_pixels * sizeof(DevPoint), (void **)&d_out[b]));
-        FUSION_HIP_TRY(hipHostMalloc((void **)&h_out[b], std::max(max_pixels, size_t(1)) * sizeof(DevPoint),
-                                     hipHostMallocDefault));
-        hold.pinned.push_back(h_out[b]);
+        FUSION_HIP_TRY(hold.dev_alloc(d_out[b], max_pixels));
+        FUSION_HIP_TRY(hold.pinned_alloc(h_out[b], std::max(max_pixels, size_t(1))));
     }
     FUSION_HIP_TRY(hipStreamSynchronize(hold.stream));
     const auto t_uploaded = Clock::now();
@@ -589,26 +645,8 @@ int fuse_on_device(Scene &sc, const JacobiCall &call, int device, Pool &pool, Cl
     };
     for (size_t i = 0; i < n; ++i) {
         const int N = sc.cols[i] * sc.rows[i];
-        const int nchunks = (N + kScanChunk - 1) / kScanChunk;
-        if (N > 0) {
-            if (prior)
-                k_prior_test<<<(N + 255) / 256, 256, 0, hold.stream>>>(d_views, (int)i, call.num_consistent_thresh,
-                                                                      call.single_match_penalty,
-                                                                      call.consistency_scalar, d_hit, d_approved);
-            else
-                k_fusion_test<<<(N + 255) / 256, 256, 0, hold.stream>>>(d_views, (int)i, call.num_consistent_thresh,
-                                                                       call.consistency_scalar, d_hit, d_approved);
-            k_fusion_chunks<<<(nchunks * 32 + 255) / 256, 256, 0, hold.stream>>>(d_hit, d_approved, N, nchunks,
-                                                                                d_chunk_last, d_chunk_count);
-        }
-        k_fusion_carry<<<1, 576, 0, hold.stream>>>(nchunks, d_chunk_last, d_chunk_count, d_carry_last, d_chunk_base,
-                                                   d_view_points + (i & 1), nullptr);
-        if (N > 0 && prior)
-            k_prior_apply<<<nchunks, kScanChunk, 0, hold.stream>>>(d_views, (int)i, d_hit, d_approved, d_chunk_base,
-                                                                   d_out[i & 1]);
-        else if (N > 0)
-            k_fusion_apply<false><<<nchunks, kScanChunk, 0, hold.stream>>>(
-                d_views, (int)i, d_hit, d_approved, d_chunk_last, d_carry_last, d_chunk_base, d_out[i & 1], DevCloud{});
+        enqueue_view(hold.stream, d_views, (int)i, N, scratch, call.rule, d_out[i & 1], DevCloud{},
+                     d_view_points + (i & 1), nullptr);
         FUSION_HIP_TRY(hipGetLastError());
         FUSION_HIP_TRY(hipMemcpyAsync(h_view_points + (i & 1), d_view_points + (i & 1), sizeof(int),
                                       hipMemcpyDeviceToHost, hold.stream));
@@ -638,40 +676,17 @@ int fuse_on_device(Scene &sc, const JacobiCall &call, int device, Pool &pool, Cl
     return rc;
 }
 
-// What acmmp_fuse_views_jacobi holds: its scratch on the device and in pinned host memory, freed on
-// every way out, once the caller's stream (borrowed, never destroyed) is through with it.
-struct FuseHold {
-    std::vector<void *> dev, pinned;
-    hipStream_t stream = nullptr;
-    bool pending = false;  // work is enqueued that the host has not waited for
-    ~FuseHold() {
-        if (pending) (void)hipStreamSynchronize(stream);
-        for (void *p : dev) (void)hipFree(p);
-        for (void *p : pinned) (void)hipHostFree(p);
-    }
-};
-
-// The checked views through the device on the caller's stream: mask words packed, then per view
-// test, chunks, carry (which adds the view's approvals to the running total) and apply (which writes
-// whole points at the total before the view + the position in it). No wait between views: the one
+// The checked views through the device on the caller's stream (borrowed): mask words packed, then
+// view by view; the carry adds the view's approvals to the running total and the apply step writes
+// whole points at the total before the view + the position in it. No wait between views: the one
 // at the end is for the count.
 int fuse_views_on_device(int device, const acmmp_fusion_view *views, int count, float consistency_scalar,
                          int con_num_thresh, const acmmp_cloud_buffers *out, hipStream_t stream,
                          int64_t *num_points) {
     const size_t n = (size_t)count;
     FUSION_HIP_TRY(hipSetDevice(device));
-    FuseHold hold;
+    DevHold hold;
     hold.stream = stream;
-    auto dev_alloc = [&](size_t bytes, void **p) -> hipError_t {
-        const hipError_t e = hipMalloc(p, std::max(bytes, size_t(256)));
-        if (e == hipSuccess) hold.dev.push_back(*p);
-        return e;
-    };
-    auto pinned_alloc = [&](size_t bytes, void **p) -> hipError_t {
-        const hipError_t e = hipHostMalloc(p, bytes, hipHostMallocDefault);
-        if (e == hipSuccess) hold.pinned.push_back(*p);
-        return e;
-    };
     auto mask_bytes = [](size_t N) { return align256((N + 63) / 64 * sizeof(uint64_t)); };
     size_t max_pixels = 0, mask_arena_bytes = 0;
     for (size_t i = 0; i < n; ++i) {
@@ -679,38 +694,25 @@ int fuse_views_on_device(int device, const acmmp_fusion_view *views, int count, 
         max_pixels = std::max(max_pixels, N);
         mask_arena_bytes += mask_bytes(N);
     }
-    const int max_chunks = (int)((max_pixels + kScanChunk - 1) / kScanChunk);
     char *d_masks = nullptr;
     DevView *d_views = nullptr, *h_views = nullptr;
-    uint32_t *d_hit = nullptr;
-    uint8_t *d_approved = nullptr;
-    int *d_chunk_last = nullptr, *d_carry_last = nullptr, *d_chunk_count = nullptr, *d_chunk_base = nullptr;
+    ViewScratch scratch;
     long long *d_total = nullptr, *h_total = nullptr;
-    FUSION_HIP_TRY(dev_alloc(mask_arena_bytes, (void **)&d_masks));
-    FUSION_HIP_TRY(dev_alloc(n * sizeof(DevView), (void **)&d_views));
-    FUSION_HIP_TRY(dev_alloc(max_pixels * sizeof(uint32_t), (void **)&d_hit));
-    FUSION_HIP_TRY(dev_alloc(max_pixels, (void **)&d_approved));
-    FUSION_HIP_TRY(dev_alloc((size_t)max_chunks * kMaxSrc * sizeof(int), (void **)&d_chunk_last));
-    FUSION_HIP_TRY(dev_alloc((size_t)max_chunks * kMaxSrc * sizeof(int), (void **)&d_carry_last));
-    FUSION_HIP_TRY(dev_alloc((size_t)max_chunks * sizeof(int), (void **)&d_chunk_count));
-    FUSION_HIP_TRY(dev_alloc((size_t)max_chunks * sizeof(int), (void **)&d_chunk_base));
-    FUSION_HIP_TRY(dev_alloc(2 * sizeof(long long), (void **)&d_total));
-    FUSION_HIP_TRY(pinned_alloc(n * sizeof(DevView), (void **)&h_views));  // pinned: the copies below do not wait
-    FUSION_HIP_TRY(pinned_alloc(sizeof(long long), (void **)&h_total));
+    FUSION_HIP_TRY(hold.dev_alloc(d_masks, mask_arena_bytes));
+    FUSION_HIP_TRY(hold.dev_alloc(d_views, n));
+    if (const int rc = alloc_scratch(hold, max_pixels, scratch)) return rc;
+    FUSION_HIP_TRY(hold.dev_alloc(d_total, 2));
+    FUSION_HIP_TRY(hold.pinned_alloc(h_views, n));  // pinned: the copies below do not wait
+    FUSION_HIP_TRY(hold.pinned_alloc(h_total, 1));
     size_t at = 0;
     for (size_t i = 0; i < n; ++i) {
         const acmmp_fusion_view &in = views[i];
         DevView &v = h_views[i];
-        v.cam = in.cam;
-        v.W = in.cam.width;
-        v.H = in.cam.height;
-        v.nsrc = in.num_src;
-        for (int j = 0; j < kMaxSrc; ++j) v.src[j] = j < v.nsrc ? in.src[j] : 0;
+        v = dev_view(in.cam, in.cam.width, in.cam.height, in.src, in.num_src);
         v.depth = in.d_depth;
         v.normal = in.d_normal;
         v.dstride = in.depth_stride;
         v.nstride = in.normal_stride;
-        v.pdepth = v.pnormal = nullptr;
         v.bgr = in.d_bgr;
         v.mask = (uint32_t *)(d_masks + at);
         at += mask_bytes((size_t)v.W * v.H);
@@ -726,18 +728,10 @@ int fuse_views_on_device(int device, const acmmp_fusion_view *views, int count, 
     DevCloud cloud{};
     if (out && out->capacity > 0) cloud = DevCloud{out->d_xyz, out->d_normal, out->d_rgb, out->capacity, nullptr};
     cloud.total = d_total;
-    for (size_t i = 0; i < n; ++i) {
-        const int N = h_views[i].W * h_views[i].H;
-        const int nchunks = (N + kScanChunk - 1) / kScanChunk;
-        k_fusion_test<<<(N + 255) / 256, 256, 0, stream>>>(d_views, (int)i, con_num_thresh, consistency_scalar, d_hit,
-                                                           d_approved);
-        k_fusion_chunks<<<(nchunks * 32 + 255) / 256, 256, 0, stream>>>(d_hit, d_approved, N, nchunks, d_chunk_last,
-                                                                        d_chunk_count);
-        k_fusion_carry<<<1, 576, 0, stream>>>(nchunks, d_chunk_last, d_chunk_count, d_carry_last, d_chunk_base, nullptr,
-                                              d_total);
-        k_fusion_apply<true><<<nchunks, kScanChunk, 0, stream>>>(d_views, (int)i, d_hit, d_approved, d_chunk_last,
-                                                                 d_carry_last, d_chunk_base, nullptr, cloud);
-    }
+    const JacobiRule rule{false, consistency_scalar, con_num_thresh, 0};
+    for (size_t i = 0; i < n; ++i)
+        enqueue_view(stream, d_views, (int)i, h_views[i].W * h_views[i].H, scratch, rule, nullptr, cloud, nullptr,
+                     d_total);
     FUSION_HIP_TRY(hipGetLastError());
     FUSION_HIP_TRY(hipMemcpyAsync(h_total, d_total + 1, sizeof(long long), hipMemcpyDeviceToHost, stream));
     FUSION_HIP_TRY(hipStreamSynchronize(stream));  // the call's one wait
@@ -769,29 +763,13 @@ int acmmp_run_fusion_jacobi(const char *dense_folder, const char *output_folder,
                             const char *image_dir, const char *mask_folder, int device, int *num_points) {
     if (!dense_folder || !output_folder || !problems || count <= 0) return ffail(ACMMP_ERR_ARG, "bad args");
     if (need_device("RunFusion", device)) return ACMMP_ERR_HIP;
-    const std::string dense = dense_folder, out = output_folder;
-    const std::string image_folder = dense + (image_dir ? image_dir : "/images");
-    const bool use_masks = mask_folder && std::string(mask_folder) != " " && mask_folder[0] != 0;
-    const char *suffix = geom_consistency ? "/depths_geom.dmb" : "/depths.dmb";
-    const size_t n = (size_t)count;
     const auto t_start = Clock::now();
-    Scene sc(problems, n);
+    Scene sc(problems, (size_t)count);
     Pool pool;
-    // the literal fusion's loads, on the pool (acmmp_run_fusion)
-    int rc = pool_for(pool, (int)n, [&](int vi) -> int {
-        const size_t i = (size_t)vi;
-        const int id = problems[i].ref_image_id;
-        const int load_rc = load_view(sc, i, image_folder, dense, result_folder(out, id), suffix);
-        if (load_rc) return load_rc;
-        sc.masks[i].assign((size_t)sc.cols[i] * sc.rows[i]);
-        if (!use_masks) return (int)ACMMP_OK;
-        return load_initial_mask(dense + "/" + mask_folder + "/" + id8(id) + ".png", sc.cols[i], sc.rows[i],
-                                 sc.masks[i]);
-    });
-    if (!rc) rc = resolve_sources(sc);
+    const int rc = load_fusion_views(sc, pool, dense_folder, output_folder, geom_consistency, image_dir, mask_folder);
     if (rc) return rc;
-    const JacobiCall call{nullptr, nullptr, consistency_scalar, con_num_thresh, 0, "RunFusionJacobi",
-                          out + "/ACMMP_model.ply"};
+    const JacobiCall call{{false, consistency_scalar, con_num_thresh, 0}, nullptr, nullptr, "RunFusionJacobi",
+                          std::string(output_folder) + "/ACMMP_model.ply"};
     return fuse_on_device(sc, call, device, pool, t_start, num_points);
 }
 
@@ -803,27 +781,18 @@ int acmmp_run_prior_aware_fusion_jacobi(const char *dense_folder, const char *ou
         return ffail(ACMMP_ERR_ARG, "bad args");
     if (need_device("RunPriorAwareFusion", device)) return ACMMP_ERR_HIP;
     const std::string dense = dense_folder, out = output_folder, fus = fusion_folder;
-    const char *suffix = geom_consistency ? "/depths_geom.dmb" : "/depths.dmb";
-    const size_t n = (size_t)count;
     const auto t_start = Clock::now();
-    FusionInputs in(problems, n);
+    FusionInputs in(problems, (size_t)count);
     Pool pool;
-    // the literal call's loads (acmmp_run_prior_aware_fusion), on the pool; masks start all zero
-    int rc = pool_for(pool, (int)n, [&](int vi) -> int {
-        const size_t i = (size_t)vi;
-        const int id = problems[i].ref_image_id;
-        int load_rc = load_view(in, i, dense + "/images", dense, result_folder(fus, id), suffix);
-        int h = 0, w = 0;
-        if (!load_rc) load_rc = read_maps(result_folder(out, id), suffix, id, in.pdepths[i], in.pnormals[i], h, w);
-        if (load_rc) return load_rc;
-        if (h != in.rows[i] || w != in.cols[i]) return ffail(ACMMP_ERR_IO, "map sizes of view %d disagree", id);
-        in.masks[i].assign((size_t)w * h);
-        return (int)ACMMP_OK;
+    int rc = pool_for(pool, count, [&](int i) -> int {  // the literal call's loads, on the pool
+        const int load_rc = load_prior_view(in, (size_t)i, dense, out, fus, depth_suffix(geom_consistency));
+        if (!load_rc) in.masks[(size_t)i].assign((size_t)in.cols[(size_t)i] * in.rows[(size_t)i]);
+        return load_rc;
     });
     if (!rc) rc = resolve_sources(in);
     if (rc) return rc;
-    const JacobiCall call{&in.pdepths, &in.pnormals, consistency_scalar, num_consistent_thresh, single_match_penalty,
-                          "RunPriorAwareFusionJacobi", out + "/ACMMP_prior_model.ply"};
+    const JacobiCall call{{true, consistency_scalar, num_consistent_thresh, single_match_penalty}, &in.pdepths,
+                          &in.pnormals, "RunPriorAwareFusionJacobi", out + "/ACMMP_prior_model.ply"};
     return fuse_on_device(in, call, device, pool, t_start, num_points);
 }
 

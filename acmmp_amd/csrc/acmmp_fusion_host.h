@@ -7,6 +7,9 @@
 //   CacheDomain, Pool, pool_for      one L3 domain: the caller walks, workers do the rest
 //   MaskBits, Scene, FusionInputs    a fusion's inputs; masks one bit a pixel
 //   load_view .. resolve_sources     one view loader and source lookup for all fusions
+//   check_view_sizes                 2^27 pixels / 32 sources: RunFusion (both orders), the device folder calls
+//   load_fusion_views                RunFusion's inputs from its raw arguments (both orders)
+//   load_prior_view                  a view of RunPriorAwareFusion, both map pairs (both orders)
 //   store_ply, store_ply_arrays      27-byte records in chunks (pool or caller)
 //   check_fusion_views               acmmp_fuse_views_jacobi's argument checks
 #ifndef ACMMP_FUSION_HOST_H_
@@ -421,6 +424,54 @@ inline int resolve_sources(Scene &sc) {
                              sc.problems[i].ref_image_id);
             sc.src_index[i].push_back(it->second);
         }
+    return ACMMP_OK;
+}
+
+// what a hit's pixel bits, the kernels' pixel indices and a hit mask's bits hold
+inline int check_view_sizes(const Scene &sc) {
+    for (size_t i = 0; i < sc.rows.size(); ++i)
+        if ((size_t)sc.cols[i] * sc.rows[i] > (size_t(1) << 27) || sc.problems[i].num_src_images > 32)
+            return ffail(ACMMP_ERR_ARG, "view %d: fusion supports images up to 2^27 pixels and 32 sources",
+                         sc.problems[i].ref_image_id);
+    return ACMMP_OK;
+}
+
+inline const char *depth_suffix(int geom_consistency) { return geom_consistency ? "/depths_geom.dmb" : "/depths.dmb"; }
+
+// RunFusion's inputs (both orders), from the call's raw arguments: the views load independently on
+// the pool (JPEG decode, two .dmb reads from output_folder, the mask if a mask folder is given), then
+// the sources
+inline int load_fusion_views(Scene &sc, Pool &pool, const char *dense_folder, const char *output_folder,
+                             int geom_consistency, const char *image_dir, const char *mask_folder) {
+    const std::string dense = dense_folder, out = output_folder;
+    const std::string image_folder = dense + (image_dir ? image_dir : "/images");
+    const bool use_masks = mask_folder && std::string(mask_folder) != " " && mask_folder[0] != 0;
+    const char *suffix = depth_suffix(geom_consistency);
+    const int rc = pool_for(pool, (int)sc.rows.size(), [&](int vi) -> int {
+        const size_t i = (size_t)vi;
+        const int id = sc.problems[i].ref_image_id;
+        const int load_rc = load_view(sc, i, image_folder, dense, result_folder(out, id), suffix);
+        if (load_rc) return load_rc;
+        sc.masks[i].assign((size_t)sc.cols[i] * sc.rows[i]);
+        if (!use_masks) return (int)ACMMP_OK;
+        return load_initial_mask(dense + "/" + mask_folder + "/" + id8(id) + ".png", sc.cols[i], sc.rows[i],
+                                 sc.masks[i]);
+    });
+    return rc ? rc : resolve_sources(sc);
+}
+
+// View i of RunPriorAwareFusion (both orders): load_view with the maps of the other reconstruction
+// (fusion_folder), and this run's (output_folder), the priors, as the second pair of the same size.
+// The masks are the caller's: mask files give 255/0 here (:654-661), never the 1 the checks test,
+// so they start all zero and only approvals mask pixels.
+inline int load_prior_view(FusionInputs &in, size_t i, const std::string &dense, const std::string &out,
+                           const std::string &fus, const char *suffix) {
+    const int id = in.problems[i].ref_image_id;
+    int rc = load_view(in, i, dense + "/images", dense, result_folder(fus, id), suffix);
+    int h = 0, w = 0;
+    if (!rc) rc = read_maps(result_folder(out, id), suffix, id, in.pdepths[i], in.pnormals[i], h, w);
+    if (rc) return rc;
+    if (h != in.rows[i] || w != in.cols[i]) return ffail(ACMMP_ERR_IO, "map sizes of view %d disagree", id);
     return ACMMP_OK;
 }
 
